@@ -21,14 +21,29 @@ Scaling: weak by default (each rank adds --seconds of audio to one longer
 file); --strong keeps one --seconds file for any world size.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--seconds S]
-                  [--config c1|c2|c3|c4|c4d|c5|c5cs4|br128] [--strong] [--no-cpu-baseline]
+                  [--config c1|c2|c3|c4|c4d|c5|c5cs4|br128] [--strong]
+                  [--dump-outputs DIR] [--full [--no-cpu-baseline]]
                   [--backend nccl|gloo]
 
-After the timed loop the last step's output is checked frame by frame against
-the oracle's SHA-256 digests of the same workload (tests/golden/
-bench_digests.json; c4 / c4d: corpus_meta.json / corpus_default_meta.json):
-"bit_exact" in the line, and a
-mismatch exits with status 3.
+A plain run sets up, warms up, times the K steps, writes the last step's output
+if --dump-outputs is given and prints the result line (the metric, ms_per_step,
+the stage clocks of the last encode).
+
+--dump-outputs DIR: rank 0 writes the .gsc bytes of the last timed step to
+DIR/gsc_bytes.npy (float32 byte values; a fixed seeded sample when the stream
+is longer than DUMP_MAX_BYTES), their count to DIR/gsc_length.npy, the sums of
+every DUMP_BLOCK bytes of the whole stream to DIR/block_sums.npy and the byte
+counts of its pieces (rank 0's frames; c4 / c4d: the files) to
+DIR/piece_sizes.npy (float64).  The input is seeded, so two builds run with the
+same arguments can be compared file by file.
+
+--full adds what takes work of its own: after the timed loop the last step's
+output is checked frame by frame against the oracle's SHA-256 digests of the
+same workload (tests/golden/bench_digests.json; c4 / c4d: corpus_meta.json /
+corpus_default_meta.json): "bit_exact" in the line, and a mismatch exits with
+status 3; the scan kernel's roofline figures (with the committed PMC / SQ
+profile summaries); and the oracle's CPU baseline (--no-cpu-baseline leaves
+that leg out).
 
 --gpus N without a launcher's WORLD_SIZE spawns N worker processes (one per
 GPU, RANK/LOCAL_RANK/WORLD_SIZE, rendezvous at 127.0.0.1) before any GPU call.
@@ -74,6 +89,9 @@ DIGESTS = ROOT / "tests" / "golden" / "bench_digests.json"  # oracle per-frame .
 # oracle .gsc digests of the lame_test files (tests/golden/make_corpus.py)
 CORPUS_META = {"c4": ROOT / "tests" / "golden" / "corpus_meta.json",
                "c4d": ROOT / "tests" / "golden" / "corpus_default_meta.json"}
+DUMP_MAX_BYTES = 15_000_000  # --dump-outputs: .gsc bytes written as float32 (60 MB of the 64 MB a dump may take)
+DUMP_BLOCK = 4096            # --dump-outputs: block_sums.npy covers the whole stream in blocks of this many bytes
+DUMP_SEED = 20250217         # the sample's index stream (a function of this seed and the stream length only)
 
 
 def _dist_env():
@@ -230,6 +248,29 @@ def frame_digest_check(key: str, frame_begin: int, blob: bytes, sizes, frames_to
     return checked, bad, len(want)
 
 
+def dump_outputs(dirpath: str, stream: bytes, piece_sizes) -> None:
+    """--dump-outputs: the .gsc bytes a caller of the timed path receives, as
+    .npy arrays (module docstring).  A stream longer than DUMP_MAX_BYTES is
+    sampled at DUMP_MAX_BYTES sorted positions drawn (with replacement) from
+    PCG64(DUMP_SEED); block_sums.npy still covers every byte."""
+    import numpy as np
+
+    d = Path(dirpath)
+    d.mkdir(parents=True, exist_ok=True)
+    data = np.frombuffer(stream, dtype=np.uint8)
+    n = data.size
+    blocks = -(-n // DUMP_BLOCK)
+    padded = np.zeros(blocks * DUMP_BLOCK, dtype=np.uint8)
+    padded[:n] = data
+    np.save(d / "block_sums.npy", padded.reshape(blocks, DUMP_BLOCK).sum(axis=1, dtype=np.float64))
+    if n > DUMP_MAX_BYTES:
+        idx = np.sort(np.random.Generator(np.random.PCG64(DUMP_SEED)).integers(0, n, DUMP_MAX_BYTES))
+        data = data[idx]
+    np.save(d / "gsc_bytes.npy", data.astype(np.float32))
+    np.save(d / "gsc_length.npy", np.array([n], dtype=np.float64))
+    np.save(d / "piece_sizes.npy", np.asarray(list(piece_sizes), dtype=np.float64))
+
+
 def oracle_ffi_first_frame_wav(wav: bytes, argv) -> bytes:
     """The first frame of a corpus file as its own WAV (the single-thread leg)."""
     import oracle_ffi
@@ -253,7 +294,12 @@ def main():
     ap.add_argument("--strong", action="store_true", help="one fixed-length file for any world size")
     ap.add_argument("--cpu-threads", type=int, default=0,
                     help="all-core CPU baseline threads (default: the job's CPU share, cgroup quota or affinity)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline leg")
+    ap.add_argument("--full", action="store_true",
+                    help="also check the last step's output against the oracle digests (bit_exact), add the scan "
+                         "kernel's roofline figures and run the CPU baseline")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the last timed step's .gsc bytes as DIR/*.npy (rank 0)")
     ap.add_argument("--share", default=None, metavar="R/N",
                     help="--strong on one GPU: encode only rank R of N's frame range of the whole file (the "
                          "PrepareFrames cut of the whole file, the range an N-GPU run gives rank R)")
@@ -263,6 +309,8 @@ def main():
                     help="torch.distributed backend for N > 1 (nccl = RCCL over xGMI; gloo rehearses the "
                          "multi-rank path on host tensors, e.g. 2 ranks on a one-GPU box)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.cpu_threads <= 0:
         args.cpu_threads = _cpu_share()[0]
 
@@ -383,7 +431,7 @@ def main():
         t = torch.tensor([dt], device=cdev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
-    # bit-exactness of the last timed step's output (after the clock stopped):
+    # bit-exactness of the last timed step's output (--full, after the clock stopped):
     # every rank checks its own frames against the oracle digests, rank 0 also
     # the length of the gathered file when every frame has a digest
     key = f"{args.config}:{total_seconds:g}"
@@ -391,17 +439,21 @@ def main():
     if os.environ.get("BENCH_DUMP"):  # diagnostic: this rank's bytes and per-frame sizes of the last step
         Path(os.environ["BENCH_DUMP"] + f".r{rank}.gsc").write_bytes(blob)
         Path(os.environ["BENCH_DUMP"] + f".r{rank}.json").write_text(json.dumps({"first": fb, "sizes": sizes}))
-    checked, bad, listed = frame_digest_check(key, fb, blob, sizes, info["frames"])
-    if dist is not None:
-        t = torch.tensor([checked, bad], dtype=torch.int64, device=cdev)
-        dist.all_reduce(t)
-        checked, bad = (int(v) for v in t.tolist())
+    checked = bad = listed = 0
+    if args.full:
+        checked, bad, listed = frame_digest_check(key, fb, blob, sizes, info["frames"])
+        if dist is not None:
+            t = torch.tensor([checked, bad], dtype=torch.int64, device=cdev)
+            dist.all_reduce(t)
+            checked, bad = (int(v) for v in t.tolist())
     if rank != 0:
         dist.destroy_process_group()
         if bad:
             sys.exit(3)
         return
-    if share is None and listed == info["frames"] and checked == listed:
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, whole, sizes)
+    if args.full and share is None and listed == info["frames"] and checked == listed:
         want_len = json.loads(DIGESTS.read_text())[key].get("total_bytes")
         if want_len is not None and len(whole) != int(want_len):
             bad += 1
@@ -423,14 +475,15 @@ def main():
     result["prepare_ms"] = round(info["prepare_ms"], 1)
     result["job_latency_ms"] = None if lat is None else round(lat, 1)
     result["realtime_x"] = round(value / (rate * ch / 1e6), 2)
-    result["bit_exact"] = (bad == 0) if checked else None
-    result["bit_exact_check"] = {
-        "digests": f"tests/golden/bench_digests.json[{key}] (oracle SaveStream bytes per frame)",
-        "frames_checked": checked, "frames_differing": bad, "frames_total": info["frames"],
-        "whole_file": checked == info["frames"],
-        "range_checked": checked == info["range"][1] - info["range"][0],
-        "note": None if checked else "no oracle digests for this workload: not checked"}
-    if not args.no_cpu_baseline:
+    if args.full:
+        result["bit_exact"] = (bad == 0) if checked else None
+        result["bit_exact_check"] = {
+            "digests": f"tests/golden/bench_digests.json[{key}] (oracle SaveStream bytes per frame)",
+            "frames_checked": checked, "frames_differing": bad, "frames_total": info["frames"],
+            "whole_file": checked == info["frames"],
+            "range_checked": checked == info["range"][1] - info["range"][0],
+            "note": None if checked else "no oracle digests for this workload: not checked"}
+    if args.full and not args.no_cpu_baseline:
         result["cpu_baseline"] = cpu_baseline(args.config, argv, rate, ch, enc.frame_length / 1000.0,
                                               args.cpu_threads)
     print(json.dumps(result))
@@ -453,7 +506,7 @@ def base_result(args, ws, dt, value, desc, enc, tm, cs, argv, rate, ch) -> dict:
     # HBM traffic of the scan kernel per launch: PMC bytes per frame (committed
     # rocprofv3 summary, gfx950-corrected) x frames in this launch
     traffic = None
-    if PMC_SUMMARY.exists():
+    if args.full and PMC_SUMMARY.exists():
         ks = json.loads(PMC_SUMMARY.read_text())["kernels"]
         kern = next((v for k, v in ks.items()
                      if k.startswith("gsc::scan_batch_kernel") and (f"<{2 * cs}, 12," in k or f"<{2 * cs}, 12>" in k)),
@@ -464,13 +517,13 @@ def base_result(args, ws, dt, value, desc, enc, tm, cs, argv, rate, ch) -> dict:
     # wave-instructions x 2 cycles / (4 SIMDs x CUs x launch cycles)) -- a profile
     # of the C2 shape, so it is attached to the C2 line only, with its source
     issue = sq = None
-    if SQ_SUMMARY.exists() and args.config == "c2":
+    if args.full and SQ_SUMMARY.exists() and args.config == "c2":
         sq = json.loads(SQ_SUMMARY.read_text())
         issue = sq.get("scan_valu_issue_frac")
     metric = "encoded Msamples/s @44.1kHz stereo ChunkSize=8 ChunkCount=4096; bit-exact .gsc"  # BASELINE.json
     if args.config != "c2":
         metric = f"encoded Msamples/s ({desc}); bit-exact .gsc"
-    return {
+    res = {
         "metric": metric,
         "value": round(value, 4),
         "unit": "Msamples/s",
@@ -511,6 +564,9 @@ def base_result(args, ws, dt, value, desc, enc, tm, cs, argv, rate, ch) -> dict:
         "scan": {"passes": tm["scan_passes"], "searches": tm["scan_point_passes"], "exact_dfs": tm["scan_slow"],
                  "solo_resolutions": tm["scan_restarts"]},
     }
+    if not args.full:  # the roofline figures (and the committed profiles they cite) belong to --full
+        del res["roofline"]
+    return res
 
 
 def bench_corpus(args, enc, argv, desc, ws, rank, cdev, dist, cs):
@@ -562,18 +618,21 @@ def bench_corpus(args, enc, argv, desc, ws, rank, cdev, dist, cs):
     result["job_latency_ms"] = None if lat is None else round(lat, 1)
     result["realtime_x"] = round(value / (44100 / 1e6), 2)
     result["outputs_bytes"] = sum(len(o) for o in outs)
-    # every file's .gsc of the last timed step against the oracle's digest
-    import hashlib
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, b"".join(outs), [len(o) for o in outs])
+    bad = 0
+    if args.full:  # every file's .gsc of the last timed step against the oracle's digest
+        import hashlib
 
-    meta_path = CORPUS_META[args.config]
-    meta = json.loads(meta_path.read_text())
-    bad = sum(hashlib.sha256(o).hexdigest() != meta["files"][n]["gsc_sha256"] for n, o in zip(names, outs))
-    if meta["argv"] != list(argv):
-        bad = len(names)
-    result["bit_exact"] = bad == 0
-    result["bit_exact_check"] = {"digests": f"tests/golden/{meta_path.name} (oracle .gsc per file)",
-                                 "files_checked": len(names), "files_differing": bad, "whole_file": True}
-    if not args.no_cpu_baseline:
+        meta_path = CORPUS_META[args.config]
+        meta = json.loads(meta_path.read_text())
+        bad = sum(hashlib.sha256(o).hexdigest() != meta["files"][n]["gsc_sha256"] for n, o in zip(names, outs))
+        if meta["argv"] != list(argv):
+            bad = len(names)
+        result["bit_exact"] = bad == 0
+        result["bit_exact_check"] = {"digests": f"tests/golden/{meta_path.name} (oracle .gsc per file)",
+                                     "files_checked": len(names), "files_differing": bad, "whole_file": True}
+    if args.full and not args.no_cpu_baseline:
         result["cpu_baseline"] = cpu_baseline(args.config, argv, 44100, 1, enc.frame_length / 1000.0, args.cpu_threads)
     print(json.dumps(result))
     if dist is not None:

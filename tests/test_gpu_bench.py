@@ -22,7 +22,7 @@ GOLD = ROOT / "tests" / "golden"
 
 def _bench(*args, timeout=400):
     r = subprocess.run([sys.executable, "-u", str(ROOT / "bench.py"), "--steps", "1", "--warmup", "0",
-                        "--no-cpu-baseline", *args], capture_output=True, text=True, timeout=timeout)
+                        "--full", "--no-cpu-baseline", *args], capture_output=True, text=True, timeout=timeout)
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert r.returncode == 0, r.stderr[-3000:]
     assert lines, r.stdout[-2000:]
@@ -40,11 +40,23 @@ def test_digest_table_covers_the_test_workloads():
 
 @pytest.mark.gpu
 @pytest.mark.timeout(420)
-def test_bench_line_is_bit_exact():
-    res = _bench("--seconds", "16")
+def test_bench_line_is_bit_exact(tmp_path):
+    res = _bench("--seconds", "16", "--dump-outputs", str(tmp_path / "dump"))
     assert res["n_gpus"] == 1 and res["bit_exact"] is True
     chk = res["bit_exact_check"]
     assert chk["whole_file"] and chk["frames_checked"] == chk["frames_total"] >= 4 and chk["frames_differing"] == 0
+    # --dump-outputs: the bit-exact stream itself, whole (16 s is far below the sampling limit)
+    import numpy as np
+
+    want = json.loads((GOLD / "bench_digests.json").read_text())["c2:16"]
+    got = {p.stem: np.load(p) for p in (tmp_path / "dump").iterdir()}
+    assert sorted(got) == ["block_sums", "gsc_bytes", "gsc_length", "piece_sizes"]
+    assert got["gsc_bytes"].dtype == np.float32 and got["gsc_bytes"].size == want["total_bytes"]
+    assert got["gsc_length"].tolist() == [want["total_bytes"]]
+    assert got["piece_sizes"].size == want["frames"] and got["piece_sizes"].sum() == want["total_bytes"]
+    assert got["block_sums"].sum() == got["gsc_bytes"].sum(dtype=np.float64)
+    h = hashlib.sha256(got["gsc_bytes"][:int(got["piece_sizes"][0])].astype(np.uint8).tobytes()).hexdigest()
+    assert h == want["per_frame"]["0"]
 
 
 @pytest.mark.gpu

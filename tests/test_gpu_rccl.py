@@ -114,7 +114,7 @@ def test_bench_takes_the_rccl_path_at_world_size_1():
     env = dict(os.environ, RANK="0", LOCAL_RANK="0", WORLD_SIZE="1", LOCAL_WORLD_SIZE="1",
                MASTER_ADDR="127.0.0.1", MASTER_PORT=str(free_port()))
     r = subprocess.run([sys.executable, "-u", str(ROOT / "bench.py"), "--steps", "1", "--warmup", "0",
-                        "--no-cpu-baseline", "--seconds", "16"], capture_output=True, text=True, timeout=400,
+                        "--full", "--no-cpu-baseline", "--seconds", "16"], capture_output=True, text=True, timeout=400,
                        env=env)
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert r.returncode == 0, r.stderr[-3000:]

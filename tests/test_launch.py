@@ -119,6 +119,39 @@ def test_bench_frame_digest_check(tmp_path, monkeypatch):
     assert bench.frame_digest_check("c2:8", 2, blob + b"!", sizes, 5)[1] == 1  # bytes past the frames
 
 
+def test_bench_dump_outputs(tmp_path, monkeypatch):
+    """bench.py --dump-outputs (host logic; the GPU test runs it on real
+    output): float32 byte values of the whole stream, or of a seeded sample
+    that depends on the stream length only; block sums over every byte."""
+    import importlib.util
+
+    spec = importlib.util.spec_from_file_location("bench_mod", ROOT / "bench.py")
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    stream = bytes(np.random.default_rng(5).integers(0, 256, 3 * bench.DUMP_BLOCK + 17, dtype=np.uint8))
+    raw = np.frombuffer(stream, dtype=np.uint8)
+
+    def dump(name, s):
+        bench.dump_outputs(str(tmp_path / name), s, [100, len(s) - 100])
+        return {p.stem: np.load(p) for p in (tmp_path / name).iterdir()}
+
+    a = dump("a", stream)
+    assert a["gsc_bytes"].dtype == np.float32 and np.array_equal(a["gsc_bytes"], raw)
+    assert all(v.dtype in (np.float32, np.float64) for v in a.values())
+    assert a["gsc_length"].tolist() == [len(stream)] and a["piece_sizes"].tolist() == [100, len(stream) - 100]
+    assert a["block_sums"].shape == (4,) and a["block_sums"][3] == raw[3 * bench.DUMP_BLOCK:].sum()
+    assert a["block_sums"].sum() == raw.sum()
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 1000)  # longer than the limit: a sample
+    b, c = dump("b", stream), dump("c", stream)
+    assert b["gsc_bytes"].shape == (1000,) and np.array_equal(b["gsc_bytes"], c["gsc_bytes"])
+    assert np.array_equal(b["block_sums"], a["block_sums"]) and b["gsc_length"].tolist() == [len(stream)]
+    other = bytearray(stream)
+    other[::7] = bytes((v + 1) % 256 for v in other[::7])  # same length: same positions, other values there
+    d = dump("d", bytes(other))
+    assert not np.array_equal(d["gsc_bytes"], b["gsc_bytes"])
+    assert (d["gsc_bytes"] != b["gsc_bytes"]).mean() == pytest.approx(1 / 7, abs=0.05)
+
+
 @pytest.mark.parametrize("args", [["--share", "1/8"], ["--share", "8/8", "--strong"],
                                   ["--share", "1/8", "--strong", "--gpus", "2"]])
 def test_bench_refuses_bad_share(args):

@@ -12,7 +12,7 @@ for c in ${CFGS:-c5 c5cs4}; do
   for s in $SH; do
     f=$O/strong_${c}_r${s%/*}of${s#*/}.log
     timeout -k 10 300 python3 -u bench.py --config $c --strong --seconds 3600 --share $s \
-      --steps ${STEPS:-2} --warmup 1 --no-cpu-baseline > $f 2>&1 || exit 3
+      --steps ${STEPS:-2} --warmup 1 --full --no-cpu-baseline > $f 2>&1 || exit 3
     tail -1 $f | cut -c1-140
   done
 done
