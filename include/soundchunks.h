@@ -196,6 +196,51 @@ typedef struct {
 } gsc_timing;
 void gsc_last_timing(gsc_timing *t);
 
+/* ---- decode: .gsc bytes -> PCM16 (decoder/decoder.lpr:37-220) ------------ */
+/* The index of a stream: one sequential host pass over the bytes (frame k + 1
+ * starts where frame k's bitstream ends; a symbol's bit offset depends on
+ * every earlier symbol of its frame).  It records every frame's offsets and
+ * fields, a checkpoint (bit offset, header state) every
+ * gsc_decode_checkpoint_symbols() symbols, and the per-frame CAttrLookup and
+ * codebook tables, and it validates everything: a truncated frame,
+ * ChunkBlend != 0, a ChunkBitDepth other than 8 / 12, ChunkSize 0, a symbol
+ * that needs bits past the end, a chunk index >= ChunkCount, or a frame whose
+ * ChannelCount / SampleRate differ from frame 0 are refused (NULL / <0 and
+ * gsc_last_error), never a fault.  Host only: works without a GPU. */
+typedef struct gsc_index gsc_index;
+gsc_index *gsc_index_create(const uint8_t *gsc, size_t len);
+int gsc_index_frame_count(const gsc_index *ix);
+int gsc_index_info(const gsc_index *ix, int *channels, int *sample_rate, long long *samples_per_channel);
+/* per frame (any pointer may be NULL): byte_offset and first_sample (per
+ * channel) receive frame_count + 1 entries, the last one the stream's length
+ * and its sample count; the others frame_count entries */
+int gsc_index_frames(const gsc_index *ix, size_t *byte_offset, int *frame_length, int *chunk_size, int *chunk_count,
+                     long long *first_sample);
+void gsc_index_free(gsc_index *ix);
+int gsc_decode_checkpoint_symbols(void);
+
+/* Frames [frame_begin, frame_end) (clamped; frame_end = -1: to the end) of an
+ * indexed stream -> PCM16 interleaved [sample][channel]: *pcm_len int16 values
+ * in *pcm (release with gsc_free).  The symbols are unpacked and the samples
+ * synthesised on the device, all frames in one launch per stage.  Ranks of a
+ * multi-GPU decode split the frames by first_sample. */
+int gsc_decode_indexed(const uint8_t *gsc, size_t len, const gsc_index *ix, int frame_begin, int frame_end,
+                       int16_t **pcm, size_t *pcm_len);
+/* index + decode of a whole stream */
+int gsc_decode(const uint8_t *gsc, size_t len, int16_t **pcm, size_t *pcm_len, int *channels, int *sample_rate);
+/* A batch of streams as one job (one launch per stage for all frames of all
+ * files; they must share ChannelCount and SampleRate): *pcm holds the files'
+ * samples back to back, file_samples[i] int16 values each. */
+int gsc_decode_many(const uint8_t *const *gscs, const size_t *lens, int file_count, int16_t **pcm,
+                    size_t *file_samples, int *channels, int *sample_rate);
+/* Timing of the last gsc_decode* call on the calling thread (milliseconds). */
+typedef struct {
+    double host_index_ms, h2d_ms, gpu_unpack_ms, gpu_synth_ms, d2h_ms, total_ms;
+    int frames;
+    long long symbols, samples; /* symbols unpacked, int16 values written */
+} gsc_decode_timing;
+void gsc_last_decode_timing(gsc_decode_timing *t);
+
 int gsc_device_count(void);
 /* bind the calling thread to a HIP device (one process per GPU) */
 int gsc_set_device(int device);

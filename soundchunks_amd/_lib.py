@@ -61,9 +61,28 @@ class GscTiming(ctypes.Structure):
     ]
 
 
+class GscDecodeTiming(ctypes.Structure):
+    """Mirror of ``gsc_decode_timing``."""
+
+    _fields_ = [
+        ("host_index_ms", ctypes.c_double),
+        ("h2d_ms", ctypes.c_double),
+        ("gpu_unpack_ms", ctypes.c_double),
+        ("gpu_synth_ms", ctypes.c_double),
+        ("d2h_ms", ctypes.c_double),
+        ("total_ms", ctypes.c_double),
+        ("frames", ctypes.c_int),
+        ("symbols", ctypes.c_longlong),
+        ("samples", ctypes.c_longlong),
+    ]
+
+
 _FP = ctypes.POINTER(ctypes.c_float)
 _IP = ctypes.POINTER(ctypes.c_int)
 _U8P = ctypes.POINTER(ctypes.c_uint8)
+_I16P = ctypes.POINTER(ctypes.c_int16)
+_SZP = ctypes.POINTER(ctypes.c_size_t)
+_LLP = ctypes.POINTER(ctypes.c_longlong)
 
 # name -> (restype, argtypes); every symbol declared in include/soundchunks.h
 SIGNATURES = {
@@ -118,6 +137,18 @@ SIGNATURES = {
     "gsc_scan_reduce": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, _FP, ctypes.c_int, _FP, _IP, ctypes.c_int, _IP]),
     "gsc_birch_labels": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, _FP, ctypes.c_int, _IP]),
     "gsc_knnfit_assign": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, _FP, ctypes.c_int, _FP, ctypes.c_float, _IP]),
+    "gsc_index_create": (ctypes.c_void_p, [_U8P, ctypes.c_size_t]),
+    "gsc_index_frame_count": (ctypes.c_int, [ctypes.c_void_p]),
+    "gsc_index_info": (ctypes.c_int, [ctypes.c_void_p, _IP, _IP, _LLP]),
+    "gsc_index_frames": (ctypes.c_int, [ctypes.c_void_p, _SZP, _IP, _IP, _IP, _LLP]),
+    "gsc_index_free": (None, [ctypes.c_void_p]),
+    "gsc_decode_checkpoint_symbols": (ctypes.c_int, []),
+    "gsc_decode_indexed": (ctypes.c_int, [_U8P, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
+                                          ctypes.POINTER(_I16P), _SZP]),
+    "gsc_decode": (ctypes.c_int, [_U8P, ctypes.c_size_t, ctypes.POINTER(_I16P), _SZP, _IP, _IP]),
+    "gsc_decode_many": (ctypes.c_int, [ctypes.POINTER(_U8P), _SZP, ctypes.c_int, ctypes.POINTER(_I16P), _SZP, _IP,
+                                       _IP]),
+    "gsc_last_decode_timing": (None, [ctypes.POINTER(GscDecodeTiming)]),
     "gsc_last_timing": (None, [ctypes.POINTER(GscTiming)]),
     "gsc_device_count": (ctypes.c_int, []),
     "gsc_set_device": (ctypes.c_int, [ctypes.c_int]),

@@ -1,0 +1,78 @@
+// .gsc decoder: the host index of a stream and the device
+// descriptors of its unpack and synthesis kernels (gsc_decode.cpp,
+// gsc_decode.hip).  The format is decoder/decoder.lpr:37-220.
+#pragma once
+#include <cstddef>
+#include <cstdint>
+#include <string>
+#include <vector>
+
+// symbols per checkpoint segment (one unpack lane walks one segment); the A/B
+// behind the value is in DESIGN.md "f5 decoder"
+#ifndef GSC_DECODE_S
+#define GSC_DECODE_S 128
+#endif
+
+namespace gsc {
+
+constexpr int kDecodeS = GSC_DECODE_S;
+// LDS of one synthesis workgroup: codebook (int16) + attenuations (bytes) of
+// a frame are staged when they fit, 4096 x 16 entries do (128 KiB + 4 KiB)
+constexpr int kDecodeLdsBytes = 136 * 1024;
+constexpr int kDecodeSynthThreads = 1024;
+
+// One frame on the device.  Offsets index the slabs of one decode call.
+struct DecFrame {
+    int64_t bs_off;    // first byte of the frame's bitstream in the byte slab
+    int64_t sym_off;   // first symbol word (idx << 2 | neg << 1 | rev) of the frame
+    int64_t out_off;   // first int16 of the frame in the output, interleaved [sample][channel]
+    int64_t cb_off;    // codebook: count * cs int16 (a multiple of 8 elements)
+    int64_t att_off;   // attenuations: count bytes
+    int64_t nsym;      // FrameLength * ChannelCount
+    int32_t cp_first;  // the frame's first checkpoint
+    int32_t ver, ch, cs, count;
+    int32_t pad_;
+    int32_t lut[32];   // CAttrLookup[negative][attenuation] (decoder.lpr:88-96)
+};
+
+// One synthesis workgroup's share of a frame: symbol rows [row0, row0 + rows),
+// a row being the ChannelCount symbols of one chunk time (cs * ch samples).
+struct DecJob {
+    int64_t row0;
+    int32_t rows;
+    int32_t frame;
+};
+
+// A checkpoint: bit offset within the frame's bitstream << 3 | (header + 1),
+// header = variableCodingHeader on entry (-1 .. 3, decoder.lpr:173-186).
+inline uint64_t make_checkpoint(uint64_t bit, int header) { return bit << 3 | uint64_t(header + 1); }
+
+struct IndexFrame {
+    size_t off = 0, att_off = 0, cb_off = 0, bs_off = 0, end_off = 0;  // byte offsets in the file
+    int ver = 0, ch = 0, count = 0, bd = 0, cs = 0, rate = 0, adiv = 0;
+    uint32_t flen = 0;         // FrameLength
+    int64_t nsym = 0;          // FrameLength * ChannelCount
+    uint64_t nbits = 0;        // bits of the bitstream (it occupies ceil(nbits / 16) words)
+    int64_t first_sample = 0;  // per channel
+    size_t cp_first = 0, cp_count = 0;  // into Index::cps
+    size_t cb_first = 0;       // into Index::codebook, a multiple of 8
+    size_t att_first = 0;      // into Index::att
+    int32_t lut[32] = {};
+};
+
+struct Index {
+    std::vector<IndexFrame> frames;
+    std::vector<uint64_t> cps;      // one per kDecodeS symbols of every frame
+    std::vector<int16_t> codebook;  // Chunks (decoder.lpr:130-158), frames padded to 8 elements
+    std::vector<uint8_t> att;       // Attenuations (decoder.lpr:115-126)
+    int channels = 0, rate = 0;
+    int64_t samples = 0;            // per channel
+    int64_t symbols = 0;
+    size_t len = 0;                 // bytes of the stream the index was built from
+};
+
+// The sequential pass (host only): frame offsets, checkpoints, lookup tables,
+// and every validation.  0, or -1 with *err set; never reads outside [g, g + len).
+int decode_walk(const uint8_t* g, size_t len, Index* ix, std::string* err);
+
+}  // namespace gsc

@@ -1,0 +1,181 @@
+// .gsc decode on MI355X (gfx950): SURVEY.md §8 f5, decoder/decoder.lpr:163-203.
+//
+//   decode_unpack_kernel  one lane per checkpoint segment (gsc_decode.cpp's
+//                         walk leaves a checkpoint every kDecodeS symbols):
+//                         reads the segment's bits from the compressed bytes
+//                         and writes one u16 word per symbol,
+//                         idx << 2 | neg << 1 | rev (pack_kernel's codes_out
+//                         and recon_kernel's chunk word)
+//   decode_synth_kernel   one lane per output sample: the low 16 bits of
+//                         (CAttrLookup[neg][att[idx]] * chunk[idx][j']) >> 15
+//                         in 32-bit arithmetic (the reference wraps, it does
+//                         not clamp), interleaved [sample][channel]
+//
+// The host validated every index and length; the kernels still clamp every
+// index and check every slab bound, so a stale index cannot make them fault.
+// The bytes are read as aligned 32-bit words of the byte slab (its base is
+// allocation-aligned and its tail zero-padded), so a bitstream may start at
+// any byte.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "gsc_decode.h"
+
+namespace gsc {
+namespace {
+
+constexpr int kUnpackThreads = 256;
+
+__global__ __launch_bounds__(kUnpackThreads) void decode_unpack_kernel(const DecFrame* __restrict__ frames, int nframes,
+                                                                       const uint64_t* __restrict__ cps, int64_t ncp,
+                                                                       const uint32_t* __restrict__ words,
+                                                                       int64_t nwords, uint16_t* __restrict__ sym,
+                                                                       int64_t nsym) {
+    const int64_t c = (int64_t)blockIdx.x * kUnpackThreads + threadIdx.x;
+    if (c >= ncp) return;
+    // the last frame whose first checkpoint is <= c (empty frames own none)
+    int lo = 0, hi = nframes - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (frames[mid].cp_first <= c) {
+            lo = mid;
+        } else {
+            hi = mid - 1;
+        }
+    }
+    const DecFrame& f = frames[lo];
+    const int64_t s0 = (c - f.cp_first) * kDecodeS;
+    if (s0 < 0 || s0 >= f.nsym) return;
+    const int n = (int)(f.nsym - s0 < kDecodeS ? f.nsym - s0 : kDecodeS);
+    const int64_t so = f.sym_off + s0;
+    if (so < 0 || so + n > nsym || f.bs_off < 0) return;
+    const uint64_t cp = cps[c];
+    int hdr = (int)(cp & 7) - 1;  // variableCodingHeader on entry
+    hdr = hdr > 3 ? 3 : hdr;
+    const uint64_t bit = (cp >> 3) + (uint64_t)f.bs_off * 8;
+    int64_t w = (int64_t)(bit >> 5);
+    const int sh = (int)(bit & 31);
+    const int rev_bit = f.ver > 0 ? 1 : 0;
+    const int idx_max = f.count > 0 ? f.count - 1 : 0;
+    uint64_t buf = (w < nwords ? words[w] : 0u) >> sh;
+    int have = 32 - sh;
+    ++w;
+    uint16_t* o = sym + so;
+    for (int i = 0; i < n; ++i) {
+        if (have <= 32) {  // refill: 33 bits or more, a symbol has at most 17
+            buf |= (uint64_t)(w < nwords ? words[w] : 0u) << have;
+            have += 32;
+            ++w;
+        }
+        const uint32_t v = (uint32_t)buf;
+        const uint32_t neg = v & 1u;
+        const uint32_t rev = rev_bit ? (v >> 1) & 1u : 0u;
+        int used = 1 + rev_bit;
+        const int has = (int)((v >> used) & 1u);
+        const int nh = (int)((v >> (used + 1)) & 3u);
+        hdr = has ? nh : hdr;
+        used += 1 + 2 * has;
+        // the next four 3-bit blocks, first block most significant; the hdr + 1
+        // leading ones are the index (no per-lane trip count: lanes stay converged)
+        const uint32_t g = v >> used;
+        const uint32_t r4 = (g & 7u) << 9 | ((g >> 3) & 7u) << 6 | ((g >> 6) & 7u) << 3 | ((g >> 9) & 7u);
+        int idx = (int)(r4 >> (3 * (3 - hdr)));
+        used += 3 * (hdr + 1);
+        buf >>= used;
+        have -= used;
+        idx = idx > idx_max ? idx_max : idx;
+        o[i] = (uint16_t)((uint32_t)idx << 2 | neg << 1 | rev);
+    }
+}
+
+__global__ __launch_bounds__(kDecodeSynthThreads) void decode_synth_kernel(
+    const DecFrame* __restrict__ frames, int nframes, const DecJob* __restrict__ jobs, int njobs, int lds_bytes,
+    const uint16_t* __restrict__ sym, int64_t nsym, const int16_t* __restrict__ cb, int64_t ncb,
+    const uint8_t* __restrict__ att, int64_t natt, int16_t* __restrict__ out, int64_t nout) {
+    extern __shared__ __align__(16) unsigned char smem[];
+    __shared__ int slut[32];
+    if ((int)blockIdx.x >= njobs) return;
+    const DecJob job = jobs[blockIdx.x];
+    if (job.frame < 0 || job.frame >= nframes) return;
+    const DecFrame& f = frames[job.frame];
+    const int cs = f.cs, ch = f.ch, count = f.count;
+    if (cs <= 0 || ch <= 0 || count <= 0 || job.rows <= 0 || job.row0 < 0) return;
+    const int row = cs * ch;
+    if ((int64_t)job.rows * row > ((int64_t)1 << 30)) return;
+    const int tid = threadIdx.x;
+    if (tid < 32) slut[tid] = f.lut[tid];
+    // the frame's codebook and attenuations in LDS when they fit
+    const int64_t cbn = (int64_t)count * cs;
+    const int64_t att_at = (cbn * 2 + 3) & ~(int64_t)3;
+    const bool staged = att_at + count <= lds_bytes && f.cb_off >= 0 && (f.cb_off & 1) == 0 &&
+                        f.cb_off + cbn + 1 <= ncb && f.att_off >= 0 && f.att_off + count <= natt;
+    const int16_t* lcb = reinterpret_cast<const int16_t*>(smem);
+    const uint8_t* latt = smem + att_at;
+    if (staged) {
+        const uint32_t* src = reinterpret_cast<const uint32_t*>(cb + f.cb_off);
+        uint32_t* dst = reinterpret_cast<uint32_t*>(smem);
+        const int nw = (int)((cbn + 1) / 2);
+        for (int i = tid; i < nw; i += kDecodeSynthThreads) dst[i] = src[i];
+        for (int i = tid; i < count; i += kDecodeSynthThreads) smem[att_at + i] = att[f.att_off + i];
+    }
+    __syncthreads();
+    const int total = job.rows * row;
+    const int64_t sym_base = f.sym_off + job.row0 * ch;
+    const int64_t out_base = f.out_off + job.row0 * row;
+    for (int l = tid; l < total; l += kDecodeSynthThreads) {
+        const int t = l / ch, k = l - t * ch;  // sample within the job, channel
+        const int q = t / cs, j = t - q * cs;  // symbol row, sample within the chunk
+        const int64_t si = sym_base + (int64_t)q * ch + k;
+        const int64_t oi = out_base + l;
+        if (si < 0 || si >= nsym || oi < 0 || oi >= nout) continue;
+        const uint32_t w = sym[si];
+        int idx = (int)(w >> 2);
+        idx = idx >= count ? count - 1 : idx;
+        const int neg = (int)((w >> 1) & 1u);
+        const int jj = (w & 1u) ? cs - 1 - j : j;
+        int a, v;
+        if (staged) {
+            a = latt[idx];
+            v = lcb[idx * cs + jj];
+        } else {
+            int64_t ai = f.att_off + idx, ci = f.cb_off + (int64_t)idx * cs + jj;
+            ai = ai < 0 ? 0 : (ai >= natt ? natt - 1 : ai);
+            ci = ci < 0 ? 0 : (ci >= ncb ? ncb - 1 : ci);
+            a = att[ai];
+            v = cb[ci];
+        }
+        // Cardinal(attr * chunkSmp) shr 15, low word (decoder.lpr:198-201)
+        out[oi] = (int16_t)(uint16_t)(((uint32_t)(slut[neg * 16 + (a & 15)] * v)) >> 15);
+    }
+}
+
+}  // namespace
+}  // namespace gsc
+
+using namespace gsc;
+
+extern "C" hipError_t gsc_launch_decode_unpack(const DecFrame* frames, int nframes, const uint64_t* cps, int64_t ncp,
+                                               const uint32_t* words, int64_t nwords, uint16_t* sym, int64_t nsym,
+                                               hipStream_t st) {
+    if (nframes <= 0 || ncp <= 0) return hipSuccess;
+    const unsigned grid = (unsigned)((ncp + kUnpackThreads - 1) / kUnpackThreads);
+    hipLaunchKernelGGL(decode_unpack_kernel, dim3(grid), dim3(kUnpackThreads), 0, st, frames, nframes, cps, ncp, words,
+                       nwords, sym, nsym);
+    return hipGetLastError();
+}
+
+extern "C" hipError_t gsc_launch_decode_synth(const DecFrame* frames, int nframes, const DecJob* jobs, int njobs,
+                                              int lds_bytes, const uint16_t* sym, int64_t nsym, const int16_t* cb,
+                                              int64_t ncb, const uint8_t* att, int64_t natt, int16_t* out, int64_t nout,
+                                              hipStream_t st) {
+    if (nframes <= 0 || njobs <= 0) return hipSuccess;
+    if (lds_bytes < 0 || lds_bytes > kDecodeLdsBytes) return hipErrorInvalidValue;
+    if (lds_bytes > 32 * 1024) {
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(decode_synth_kernel),
+                                                 hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(decode_synth_kernel, dim3((unsigned)njobs), dim3(kDecodeSynthThreads), (size_t)lds_bytes, st,
+                       frames, nframes, jobs, njobs, lds_bytes, sym, nsym, cb, ncb, att, natt, out, nout);
+    return hipGetLastError();
+}
