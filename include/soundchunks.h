@@ -218,6 +218,15 @@ int gsc_index_frames(const gsc_index *ix, size_t *byte_offset, int *frame_length
                      long long *first_sample);
 void gsc_index_free(gsc_index *ix);
 int gsc_decode_checkpoint_symbols(void);
+/* Where per-channel sample position `sample` in [0, samples) lives (any
+ * pointer may be NULL): the frame that contains it (frames of FrameLength 0
+ * contain nothing and are skipped), the symbol row inside that frame,
+ * (sample - first_sample) / ChunkSize, the position inside the chunk, and the
+ * index of the checkpoint the row's first symbol belongs to, counted over the
+ * whole stream: cp_first + row * ChannelCount / checkpoint_symbols.  A
+ * position outside [0, samples) is refused (<0 and gsc_last_error).  Host only. */
+int gsc_index_locate(const gsc_index *ix, long long sample, int *frame, long long *row, int *within,
+                     long long *checkpoint);
 
 /* Frames [frame_begin, frame_end) (clamped; frame_end = -1: to the end) of an
  * indexed stream -> PCM16 interleaved [sample][channel]: *pcm_len int16 values
@@ -233,11 +242,72 @@ int gsc_decode(const uint8_t *gsc, size_t len, int16_t **pcm, size_t *pcm_len, i
  * samples back to back, file_samples[i] int16 values each. */
 int gsc_decode_many(const uint8_t *const *gscs, const size_t *lens, int file_count, int16_t **pcm,
                     size_t *file_samples, int *channels, int *sample_rate);
-/* Timing of the last gsc_decode* call on the calling thread (milliseconds). */
+
+/* ---- resident streams: sample ranges into device memory --------------------- */
+/* gsc_stream_open walks the stream (as gsc_index_create) and uploads, once, the
+ * byte slab, the checkpoints, the int16 codebooks, the attenuations and the
+ * frame table to the calling thread's device, where they stay until
+ * gsc_stream_free (which first waits for the device's queued work).  NULL and
+ * gsc_last_error on a malformed stream or without a device. */
+typedef struct gsc_stream gsc_stream;
+gsc_stream *gsc_stream_open(const uint8_t *gsc, size_t len);
+void gsc_stream_free(gsc_stream *st);
+int gsc_stream_info(const gsc_stream *st, int *channels, int *sample_rate, long long *samples_per_channel,
+                    int *frames);
+/* the index inside (owned by the stream; do not free) */
+const gsc_index *gsc_stream_index(const gsc_stream *st);
+/* the HIP device the stream's memory lives on (a caller checks its output
+ * buffer against it; gsc_decode_crops refuses a stream of another device) */
+int gsc_stream_device(const gsc_stream *st);
+
+/* `count` samples per channel from position `begin` of streams[stream] */
+typedef struct {
+    int stream;
+    long long begin;
+    long long count;
+} gsc_crop;
+enum { GSC_PCM_INT16 = 0, GSC_PCM_FLOAT32 = 1 };  /* float32 = int16 * 2^-15, exact */
+enum { GSC_LAYOUT_TC = 0, GSC_LAYOUT_CT = 1 };    /* [B][T][C] interleaved, [B][C][T] planar; T = length */
+/* Crop i fills row i of dst_device (device memory of ncrops * length *
+ * channels elements of `dtype` in `layout`).  A crop that runs past the end of
+ * its stream is clipped there: written[i] (may be NULL) is the clipped length,
+ * and the rest of the row up to `length` is zero.  Refused, with nothing
+ * launched (<0 and gsc_last_error): begin < 0, begin > samples, count < 0,
+ * count > length, a stream index outside [0, nstreams), streams whose channel
+ * counts differ, a NULL dst_device, an unknown dtype or layout, and a stream
+ * that lives on another device than the calling thread's.  Streams may differ
+ * in sample rate, ChunkSize and bit depth.  All crops run in one launch
+ * (unpack of the checkpoint segments the crops touch and synthesis, fused),
+ * enqueued on hip_stream (a hipStream_t; NULL: the default stream) and ordered
+ * with it: the call contains no device synchronisation and copies no sample
+ * to the host.  It uploads only its job descriptors; its scratch is allocated
+ * and freed in stream order, so calls on different streams share nothing.
+ * The descriptors are uploaded with hipMemcpyAsync from pageable memory: the
+ * runtime stages a copy that small (about 100 bytes per crop), but where it
+ * cannot, HIP may complete the copy before returning, and the call then waits
+ * for the work queued earlier on hip_stream (never for other streams).
+ * written[] is filled only when everything was enqueued. */
+int gsc_decode_crops(gsc_stream *const *streams, int nstreams, const gsc_crop *crops, int ncrops, int dtype,
+                     int layout, long long length, void *dst_device, void *hip_stream, long long *written);
+/* [begin, begin + count) of one stream -> count * channels int16 in host
+ * memory `pcm`, interleaved: the crop decode into device scratch and one
+ * download.  The range must lie inside the stream. */
+int gsc_stream_decode_samples(gsc_stream *st, long long begin, long long count, int16_t *pcm);
+/* Measurement knob, per thread; NOT a stable part of the interface (it exists
+ * for the A/B in DESIGN.md and may go once a size rule replaces it).  How
+ * gsc_decode_crops runs: 0 unpack, then synthesis with the codebook read from
+ * global memory; 1 the same with each frame's codebook staged in LDS; 2
+ * unpack and synthesis fused in one launch (default).  Returns the previous
+ * value; any other argument only queries.  The output does not depend on it. */
+int gsc_decode_crops_variant(int variant);
+
+/* Timing of the last gsc_decode*, gsc_stream_open or crop call on the calling
+ * thread (milliseconds).  h2d_bytes: the bytes that call uploaded. */
 typedef struct {
     double host_index_ms, h2d_ms, gpu_unpack_ms, gpu_synth_ms, d2h_ms, total_ms;
     int frames;
     long long symbols, samples; /* symbols unpacked, int16 values written */
+    long long h2d_bytes;
 } gsc_decode_timing;
 void gsc_last_decode_timing(gsc_decode_timing *t);
 

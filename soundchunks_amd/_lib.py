@@ -74,7 +74,18 @@ class GscDecodeTiming(ctypes.Structure):
         ("frames", ctypes.c_int),
         ("symbols", ctypes.c_longlong),
         ("samples", ctypes.c_longlong),
+        ("h2d_bytes", ctypes.c_longlong),
     ]
+
+
+class GscCrop(ctypes.Structure):
+    """Mirror of ``gsc_crop``: per-channel sample positions of one stream."""
+
+    _fields_ = [("stream", ctypes.c_int), ("begin", ctypes.c_longlong), ("count", ctypes.c_longlong)]
+
+
+PCM_INT16, PCM_FLOAT32 = 0, 1
+LAYOUT_TC, LAYOUT_CT = 0, 1
 
 
 _FP = ctypes.POINTER(ctypes.c_float)
@@ -143,6 +154,17 @@ SIGNATURES = {
     "gsc_index_frames": (ctypes.c_int, [ctypes.c_void_p, _SZP, _IP, _IP, _IP, _LLP]),
     "gsc_index_free": (None, [ctypes.c_void_p]),
     "gsc_decode_checkpoint_symbols": (ctypes.c_int, []),
+    "gsc_index_locate": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_longlong, _IP, _LLP, _IP, _LLP]),
+    "gsc_stream_open": (ctypes.c_void_p, [_U8P, ctypes.c_size_t]),
+    "gsc_stream_free": (None, [ctypes.c_void_p]),
+    "gsc_stream_info": (ctypes.c_int, [ctypes.c_void_p, _IP, _IP, _LLP, _IP]),
+    "gsc_stream_index": (ctypes.c_void_p, [ctypes.c_void_p]),
+    "gsc_stream_device": (ctypes.c_int, [ctypes.c_void_p]),
+    "gsc_decode_crops": (ctypes.c_int, [ctypes.POINTER(ctypes.c_void_p), ctypes.c_int, ctypes.POINTER(GscCrop),
+                                        ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_longlong, ctypes.c_void_p,
+                                        ctypes.c_void_p, _LLP]),
+    "gsc_stream_decode_samples": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_longlong, ctypes.c_longlong, _I16P]),
+    "gsc_decode_crops_variant": (ctypes.c_int, [ctypes.c_int]),
     "gsc_decode_indexed": (ctypes.c_int, [_U8P, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
                                           ctypes.POINTER(_I16P), _SZP]),
     "gsc_decode": (ctypes.c_int, [_U8P, ctypes.c_size_t, ctypes.POINTER(_I16P), _SZP, _IP, _IP]),

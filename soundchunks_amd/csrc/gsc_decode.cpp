@@ -10,9 +10,16 @@
 // there on everything is parallel: one device lane unpacks one checkpoint
 // segment, one lane writes one output sample (gsc_decode.hip).
 //
-// GSC_DECODE_WALK_ONLY builds the walk alone (no HIP), for host-side checks.
+// A resident stream (gsc_stream_open) keeps the walk's result and the bytes
+// on the device; gsc_decode_crops then decodes batches of sample ranges from
+// the checkpoints at or before them (index_locate, plan_crops here;
+// gsc_decode_crops.hip) into caller-owned device memory.
+//
+// GSC_DECODE_WALK_ONLY builds the walk, the sample locator and the crop
+// planner alone (no HIP), for host-side checks.
 #include "gsc_decode.h"
 
+#include <algorithm>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -186,6 +193,98 @@ int decode_walk(const uint8_t* g, size_t len, Index* ix, std::string* err) {
     return 0;
 }
 
+int index_locate(const Index& ix, int64_t sample, int* frame, int64_t* row, int* within, int64_t* checkpoint,
+                 std::string* err) {
+    if (sample < 0 || sample >= ix.samples) {
+        if (err)
+            *err = "gsc locate: sample " + std::to_string(sample) + " outside [0, " + std::to_string(ix.samples) + ")";
+        return -1;
+    }
+    // the last frame whose first sample is <= sample: of a run of frames that
+    // start at the same sample, all but the last are empty
+    size_t lo = 0, hi = ix.frames.size() - 1;
+    while (lo < hi) {
+        const size_t mid = (lo + hi + 1) / 2;
+        if (ix.frames[mid].first_sample <= sample) {
+            lo = mid;
+        } else {
+            hi = mid - 1;
+        }
+    }
+    const IndexFrame& f = ix.frames[lo];
+    const int64_t local = sample - f.first_sample;
+    const int64_t r = local / f.cs;
+    if (frame) *frame = int(lo);
+    if (row) *row = r;
+    if (within) *within = int(local - r * f.cs);
+    if (checkpoint) *checkpoint = int64_t(f.cp_first) + r * f.ch / kDecodeS;
+    return 0;
+}
+
+int plan_crops(const Index* const* ixs, int nstreams, const Crop* crops, int ncrops, int64_t length, CropPlan* plan,
+               std::string* err) {
+    *plan = CropPlan();
+    auto refuse = [&](int i, const std::string& what) {
+        if (err) *err = "gsc crops: crop " + std::to_string(i) + ": " + what;
+        return -1;
+    };
+    if (!ixs || nstreams <= 0 || ncrops < 0 || (ncrops > 0 && !crops) || length < 0) {
+        if (err) *err = "gsc crops: invalid argument";
+        return -1;
+    }
+    for (int s = 0; s < nstreams; ++s) {
+        if (!ixs[s]) {
+            if (err) *err = "gsc crops: stream " + std::to_string(s) + " is null";
+            return -1;
+        }
+        if (ixs[s]->channels != ixs[0]->channels) {
+            if (err)
+                *err = "gsc crops: stream " + std::to_string(s) + " has " + std::to_string(ixs[s]->channels) +
+                       " channels, stream 0 has " + std::to_string(ixs[0]->channels);
+            return -1;
+        }
+    }
+    plan->channels = ixs[0]->channels;
+    plan->crops.reserve(size_t(ncrops));
+    for (int i = 0; i < ncrops; ++i) {
+        const Crop& c = crops[i];
+        if (c.stream < 0 || c.stream >= nstreams) return refuse(i, "stream index " + std::to_string(c.stream));
+        const Index& ix = *ixs[c.stream];
+        if (c.begin < 0 || c.begin > ix.samples)
+            return refuse(i, "begin " + std::to_string(c.begin) + " outside [0, " + std::to_string(ix.samples) + "]");
+        if (c.count < 0 || c.count > length)
+            return refuse(i, "count " + std::to_string(c.count) + " outside [0, length " + std::to_string(length) + "]");
+        PlanCrop pc{c.stream, c.begin, std::min<int64_t>(c.count, ix.samples - c.begin), 0, 0, int(plan->pieces.size())};
+        if (pc.count > 0) {
+            int fa = 0, fb = 0;
+            int64_t ra = 0, rb = 0;
+            if (index_locate(ix, pc.begin, &fa, &ra, nullptr, nullptr, err) != 0 ||
+                index_locate(ix, pc.begin + pc.count - 1, &fb, &rb, nullptr, nullptr, err) != 0)
+                return -1;
+            pc.f0 = fa;
+            pc.f1 = fb + 1;
+            for (int fi = fa; fi <= fb; ++fi) {
+                const IndexFrame& f = ix.frames[size_t(fi)];
+                CropPiece p{plan->slots, 0, 0, i, fi, 0};
+                if (f.nsym > 0) {
+                    // symbol rows [r0, r1] of this frame, whole checkpoint segments around them
+                    const int64_t r0 = fi == fa ? ra : 0, r1 = fi == fb ? rb : int64_t(f.flen) - 1;
+                    p.seg0 = r0 * f.ch / kDecodeS;
+                    p.nseg = int32_t(((r1 + 1) * f.ch - 1) / kDecodeS - p.seg0 + 1);
+                }
+                plan->slots += p.nseg;
+                plan->pieces.push_back(p);
+            }
+        }
+        plan->crops.push_back(pc);
+    }
+    if (plan->pieces.size() >= (size_t(1) << 31) || plan->slots >= (int64_t(1) << 40)) {
+        if (err) *err = "gsc crops: too many frames or symbols for one call";
+        return -1;
+    }
+    return 0;
+}
+
 }  // namespace gsc
 
 #ifndef GSC_DECODE_WALK_ONLY
@@ -208,8 +307,32 @@ extern "C" hipError_t gsc_launch_decode_synth(const gsc::DecFrame* frames, int n
                                               const int16_t* cb, int64_t ncb, const uint8_t* att, int64_t natt,
                                               int16_t* out, int64_t nout, hipStream_t st);
 
+extern "C" hipError_t gsc_launch_crop_unpack(const gsc::CropJob* jobs, int ncrops, const gsc::CropPiece* pieces,
+                                             int npieces, uint16_t* sym, int64_t nslots, hipStream_t st);
+extern "C" hipError_t gsc_launch_crop_synth(const gsc::CropJob* jobs, int ncrops, const gsc::CropPiece* pieces,
+                                            int npieces, const uint16_t* sym, int64_t nslots, int64_t length,
+                                            int channels, int is_float, int planar, int lds_bytes, int tile_len,
+                                            void* out, hipStream_t st);
+extern "C" hipError_t gsc_launch_crop_fused(const gsc::CropJob* jobs, int ncrops, int64_t length, int channels,
+                                            int is_float, int planar, int tile_len, void* out, hipStream_t st);
+
 struct gsc_index {
     gsc::Index ix;
+};
+
+// A stream resident on one device: the index, and on the device the byte slab
+// (whole words, zero tail), every checkpoint, the int16 codebooks, the
+// attenuations and the frame table, until gsc_stream_free.
+struct gsc_stream {
+    gsc_index idx;
+    int device = 0;
+    int lds_bytes = 0;  // the largest staged codebook + attenuations of a frame
+    uint8_t* d_bytes = nullptr;
+    uint8_t* d_att = nullptr;
+    uint64_t* d_cps = nullptr;
+    int16_t* d_cb = nullptr;
+    gsc::ResFrame* d_frames = nullptr;
+    int64_t nwords = 0, ncp = 0, ncb = 0, natt = 0;
 };
 
 namespace gsc {
@@ -220,6 +343,9 @@ int require_device();
 namespace {
 
 thread_local gsc_decode_timing t_dtim;
+// crop decode: 0 unpack, then synthesis with the codebook from global memory; 1 the same with the codebook
+// staged in LDS; 2 unpack and synthesis fused in one launch (DESIGN.md "f5 decoder" has the A/B)
+thread_local int t_crop_variant = 2;
 
 double now_ms() {
     return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
@@ -386,6 +512,8 @@ int decode_parts(const std::vector<Part>& parts, int16_t** pcm, size_t* pcm_len,
         DEC_TRY(hipMemcpy(d_frames.p, frames.data(), frames.size() * sizeof(DecFrame), hipMemcpyHostToDevice));
         DEC_TRY(hipMemcpy(d_jobs.p, jobs.data(), jobs.size() * sizeof(DecJob), hipMemcpyHostToDevice));
         DEC_TRY(hipDeviceSynchronize());
+        tim->h2d_bytes = (long long)(nbytes + ncp * sizeof(uint64_t) + ncb * sizeof(int16_t) + natt +
+                                     frames.size() * sizeof(DecFrame) + jobs.size() * sizeof(DecJob));
         const double t1 = now_ms();
         DEC_TRY(hipEventRecord(e0.e, nullptr));
         DEC_TRY(gsc_launch_decode_unpack(d_frames.p, int(frames.size()), d_cps.p, int64_t(ncp),
@@ -513,6 +641,246 @@ int gsc_decode_many(const uint8_t* const* gscs, const size_t* lens, int file_cou
 
 void gsc_last_decode_timing(gsc_decode_timing* t) {
     if (t) *t = t_dtim;
+}
+
+int gsc_index_locate(const gsc_index* ix, long long sample, int* frame, long long* row, int* within,
+                     long long* checkpoint) {
+    if (!ix) return set_last_error("null index");
+    std::string err;
+    int64_t r = 0, c = 0;
+    if (index_locate(ix->ix, sample, frame, &r, within, &c, &err) != 0) return set_last_error(err);
+    if (row) *row = r;
+    if (checkpoint) *checkpoint = c;
+    return 0;
+}
+
+void gsc_stream_free(gsc_stream* st) {
+    if (!st) return;
+    int cur = 0;
+    const bool sw = hipGetDevice(&cur) == hipSuccess && cur != st->device;
+    if (sw) (void)hipSetDevice(st->device);
+    (void)hipDeviceSynchronize();  // queued crop decodes still read the slabs
+    (void)hipFree(st->d_bytes);
+    (void)hipFree(st->d_att);
+    (void)hipFree(st->d_cps);
+    (void)hipFree(st->d_cb);
+    (void)hipFree(st->d_frames);
+    if (sw) (void)hipSetDevice(cur);
+    delete st;
+}
+
+#define STREAM_TRY(expr)                                                                   \
+    do {                                                                                   \
+        hipError_t e_ = (expr);                                                            \
+        if (e_ != hipSuccess) {                                                            \
+            set_last_error(std::string(#expr) + ": " + hipGetErrorString(e_));             \
+            gsc_stream_free(h);                                                            \
+            return nullptr;                                                                \
+        }                                                                                  \
+    } while (0)
+
+gsc_stream* gsc_stream_open(const uint8_t* gsc, size_t len) {
+    t_dtim = gsc_decode_timing{};
+    const double t0 = now_ms();
+    gsc_stream* h = new gsc_stream();
+    std::string err;
+    if (decode_walk(gsc, len, &h->idx.ix, &err) != 0) {
+        delete h;
+        set_last_error(err);
+        return nullptr;
+    }
+    const Index& ix = h->idx.ix;
+    t_dtim.host_index_ms = now_ms() - t0;
+    if (require_device() != 0) {
+        delete h;
+        return nullptr;
+    }
+    STREAM_TRY(hipGetDevice(&h->device));
+    std::vector<ResFrame> frames(ix.frames.size());
+    for (size_t i = 0; i < frames.size(); ++i) {
+        const IndexFrame& f = ix.frames[i];
+        ResFrame& d = frames[i];
+        d = ResFrame{};
+        d.bs_off = int64_t(f.bs_off);
+        d.cb_off = int64_t(f.cb_first);
+        d.att_off = int64_t(f.att_first);
+        d.nsym = f.nsym;
+        d.first_sample = f.first_sample;
+        d.cp_first = int64_t(f.cp_first);
+        d.ver = f.ver;
+        d.ch = f.ch;
+        d.cs = f.cs;
+        d.count = f.count;
+        std::memcpy(d.lut, f.lut, sizeof(d.lut));
+        const int64_t need = ((int64_t(f.count) * f.cs * 2 + 3) & ~int64_t(3)) + f.count;
+        if (f.flen > 0 && need <= kDecodeLdsBytes) h->lds_bytes = std::max(h->lds_bytes, int(need));
+    }
+    const double t1 = now_ms();
+    const size_t byte_alloc = ((len + 3) & ~size_t(3)) + 16;  // whole words, zero tail
+    h->nwords = int64_t(byte_alloc / 4);
+    h->ncp = int64_t(ix.cps.size());
+    h->ncb = int64_t(ix.codebook.size() + 16);
+    h->natt = int64_t(ix.att.size() + 1);
+    STREAM_TRY(hipMalloc(reinterpret_cast<void**>(&h->d_bytes), byte_alloc));
+    STREAM_TRY(hipMalloc(reinterpret_cast<void**>(&h->d_att), size_t(h->natt)));
+    STREAM_TRY(hipMalloc(reinterpret_cast<void**>(&h->d_cps), std::max<size_t>(ix.cps.size(), 1) * sizeof(uint64_t)));
+    STREAM_TRY(hipMalloc(reinterpret_cast<void**>(&h->d_cb), size_t(h->ncb) * sizeof(int16_t)));
+    STREAM_TRY(hipMalloc(reinterpret_cast<void**>(&h->d_frames), std::max<size_t>(frames.size(), 1) * sizeof(ResFrame)));
+    STREAM_TRY(hipMemset(h->d_bytes + (len & ~size_t(3)), 0, byte_alloc - (len & ~size_t(3))));
+    STREAM_TRY(hipMemset(h->d_cb + ix.codebook.size(), 0, 16 * sizeof(int16_t)));
+    STREAM_TRY(hipMemset(h->d_att + ix.att.size(), 0, 1));
+    STREAM_TRY(hipMemcpy(h->d_bytes, gsc, len, hipMemcpyHostToDevice));
+    if (!ix.cps.empty())
+        STREAM_TRY(hipMemcpy(h->d_cps, ix.cps.data(), ix.cps.size() * sizeof(uint64_t), hipMemcpyHostToDevice));
+    if (!ix.codebook.empty())
+        STREAM_TRY(hipMemcpy(h->d_cb, ix.codebook.data(), ix.codebook.size() * sizeof(int16_t), hipMemcpyHostToDevice));
+    if (!ix.att.empty()) STREAM_TRY(hipMemcpy(h->d_att, ix.att.data(), ix.att.size(), hipMemcpyHostToDevice));
+    STREAM_TRY(hipMemcpy(h->d_frames, frames.data(), frames.size() * sizeof(ResFrame), hipMemcpyHostToDevice));
+    STREAM_TRY(hipDeviceSynchronize());
+    t_dtim.h2d_ms = now_ms() - t1;
+    t_dtim.h2d_bytes = (long long)(len + ix.cps.size() * sizeof(uint64_t) + ix.codebook.size() * sizeof(int16_t) +
+                                   ix.att.size() + frames.size() * sizeof(ResFrame));
+    t_dtim.frames = int(frames.size());
+    t_dtim.total_ms = now_ms() - t0;
+    return h;
+}
+
+int gsc_stream_info(const gsc_stream* st, int* channels, int* sample_rate, long long* samples_per_channel,
+                    int* frames) {
+    if (!st) return set_last_error("null stream");
+    if (channels) *channels = st->idx.ix.channels;
+    if (sample_rate) *sample_rate = st->idx.ix.rate;
+    if (samples_per_channel) *samples_per_channel = st->idx.ix.samples;
+    if (frames) *frames = int(st->idx.ix.frames.size());
+    return 0;
+}
+
+const gsc_index* gsc_stream_index(const gsc_stream* st) {
+    if (!st) {
+        set_last_error("null stream");
+        return nullptr;
+    }
+    return &st->idx;
+}
+
+int gsc_stream_device(const gsc_stream* st) { return st ? st->device : set_last_error("null stream"); }
+
+int gsc_decode_crops_variant(int variant) {
+    const int prev = t_crop_variant;
+    if (variant >= 0 && variant <= 2) t_crop_variant = variant;
+    return prev;
+}
+
+int gsc_decode_crops(gsc_stream* const* streams, int nstreams, const gsc_crop* crops, int ncrops, int dtype,
+                     int layout, long long length, void* dst_device, void* hip_stream, long long* written) {
+    const double t_begin = now_ms();
+    t_dtim = gsc_decode_timing{};
+    if (!streams || nstreams <= 0) return set_last_error("gsc_decode_crops: no streams");
+    if (dtype != GSC_PCM_INT16 && dtype != GSC_PCM_FLOAT32) return set_last_error("gsc_decode_crops: unknown dtype");
+    if (layout != GSC_LAYOUT_TC && layout != GSC_LAYOUT_CT) return set_last_error("gsc_decode_crops: unknown layout");
+    if (!dst_device) return set_last_error("gsc_decode_crops: dst_device is null");
+    std::vector<const Index*> ixs(static_cast<size_t>(nstreams), nullptr);
+    for (int s = 0; s < nstreams; ++s) {
+        if (!streams[s]) return set_last_error("gsc_decode_crops: stream " + std::to_string(s) + " is null");
+        ixs[size_t(s)] = &streams[s]->idx.ix;
+    }
+    std::vector<Crop> cr(static_cast<size_t>(std::max(ncrops, 0)));
+    if (ncrops > 0 && !crops) return set_last_error("gsc_decode_crops: crops is null");
+    for (int i = 0; i < ncrops; ++i) cr[size_t(i)] = Crop{crops[i].stream, crops[i].begin, crops[i].count};
+    CropPlan plan;
+    std::string err;
+    if (plan_crops(ixs.data(), nstreams, cr.data(), ncrops, length, &plan, &err) != 0) return set_last_error(err);
+    if (require_device() != 0) return -1;
+    int dev = 0;
+    DEC_TRY(hipGetDevice(&dev));
+    for (int s = 0; s < nstreams; ++s)
+        if (streams[s]->device != dev)
+            return set_last_error("gsc_decode_crops: stream " + std::to_string(s) + " lives on device " +
+                                  std::to_string(streams[s]->device) + ", the calling thread is bound to device " +
+                                  std::to_string(dev));
+    auto report = [&] {  // only once everything is enqueued: a failed call reports no output
+        for (int i = 0; i < ncrops; ++i)
+            if (written) written[i] = plan.crops[size_t(i)].count;
+        return 0;
+    };
+    if (ncrops == 0 || length == 0) return report();
+    const int C = plan.channels;
+    if (C <= 0 || length > (int64_t(1) << 40) / (int64_t(ncrops) * C))
+        return set_last_error("gsc_decode_crops: output too large for one call");
+    hipStream_t hs = static_cast<hipStream_t>(hip_stream);
+    // the call's own block: job descriptors, then the symbol scratch; stream-ordered, so calls on other
+    // streams never share it
+    const size_t njob = size_t(ncrops), npc = plan.pieces.size();
+    const size_t desc_bytes = (njob * sizeof(CropJob) + npc * sizeof(CropPiece) + 15) & ~size_t(15);
+    const bool fused = t_crop_variant == 2;  // no symbol scratch
+    const size_t sym_bytes = fused ? 0 : size_t(plan.slots) * kDecodeS * sizeof(uint16_t);
+    std::vector<unsigned char> host(desc_bytes, 0);
+    CropJob* hj = reinterpret_cast<CropJob*>(host.data());
+    int lds_bytes = 0;
+    for (size_t i = 0; i < njob; ++i) {
+        const PlanCrop& pc = plan.crops[i];
+        const gsc_stream& st = *streams[pc.stream];
+        hj[i] = CropJob{st.d_frames, st.d_cps,   reinterpret_cast<const uint32_t*>(st.d_bytes),
+                        st.d_cb,     st.d_att,   st.ncp,
+                        st.nwords,   st.ncb,     st.natt,
+                        pc.begin,    pc.count,   int32_t(st.idx.ix.frames.size()),
+                        pc.f0,       pc.f1,      pc.piece0};
+        lds_bytes = std::max(lds_bytes, st.lds_bytes);
+    }
+    if (npc) std::memcpy(host.data() + njob * sizeof(CropJob), plan.pieces.data(), npc * sizeof(CropPiece));
+    unsigned char* d_block = nullptr;
+    DEC_TRY(hipMallocAsync(reinterpret_cast<void**>(&d_block), desc_bytes + std::max<size_t>(sym_bytes, 16), hs));
+    struct FreeAsync {
+        unsigned char* p;
+        hipStream_t s;
+        ~FreeAsync() { (void)hipFreeAsync(p, s); }
+    } guard{d_block, hs};
+    // pageable source: the runtime has taken the bytes when the call returns (it stages a small copy;
+    // one it cannot stage it completes first, and then this call waits for the stream's earlier work)
+    DEC_TRY(hipMemcpyAsync(d_block, host.data(), desc_bytes, hipMemcpyHostToDevice, hs));
+    const CropJob* d_jobs = reinterpret_cast<const CropJob*>(d_block);
+    const CropPiece* d_pieces = reinterpret_cast<const CropPiece*>(d_block + njob * sizeof(CropJob));
+    uint16_t* d_sym = reinterpret_cast<uint16_t*>(d_block + desc_bytes);
+    const int is_float = dtype == GSC_PCM_FLOAT32, planar = layout == GSC_LAYOUT_CT;
+    if (fused) {
+        // a workgroup per 4 Ki samples of a crop: 8 or 9 segments of a stereo ChunkSize-8 stream
+        DEC_TRY(gsc_launch_crop_fused(d_jobs, ncrops, length, C, is_float, planar, int(std::min<int64_t>(length, 4096)),
+                                      dst_device, hs));
+    } else {
+        DEC_TRY(gsc_launch_crop_unpack(d_jobs, ncrops, d_pieces, int(npc), d_sym, plan.slots, hs));
+        // LDS variant: a workgroup per 16 Ki samples of a crop
+        DEC_TRY(gsc_launch_crop_synth(d_jobs, ncrops, d_pieces, int(npc), d_sym, plan.slots, length, C, is_float,
+                                      planar, t_crop_variant == 1 ? lds_bytes : -1,
+                                      int(std::min<int64_t>(length, 16384)), dst_device, hs));
+    }
+    t_dtim.h2d_bytes = (long long)desc_bytes;
+    t_dtim.frames = int(npc);
+    t_dtim.symbols = plan.slots * kDecodeS;
+    t_dtim.samples = int64_t(ncrops) * length * C;
+    t_dtim.total_ms = now_ms() - t_begin;
+    return report();
+}
+
+int gsc_stream_decode_samples(gsc_stream* st, long long begin, long long count, int16_t* pcm) {
+    if (!st || (!pcm && count > 0)) return set_last_error("gsc_stream_decode_samples: invalid argument");
+    if (begin < 0 || count < 0 || begin > st->idx.ix.samples || count > st->idx.ix.samples - begin)
+        return set_last_error("gsc_stream_decode_samples: [" + std::to_string(begin) + ", " +
+                              std::to_string(begin) + " + " + std::to_string(count) + ") outside the stream's " +
+                              std::to_string(st->idx.ix.samples) + " samples");
+    if (count == 0) return 0;
+    if (require_device() != 0) return -1;
+    const size_t n = size_t(count) * size_t(st->idx.ix.channels);
+    Dev<int16_t> d_out;
+    DEC_TRY(d_out.alloc(n));
+    gsc_crop c{0, begin, count};
+    gsc_stream* one[1] = {st};
+    if (gsc_decode_crops(one, 1, &c, 1, GSC_PCM_INT16, GSC_LAYOUT_TC, count, d_out.p, nullptr, nullptr) != 0)
+        return -1;
+    const double t0 = now_ms();
+    DEC_TRY(hipMemcpy(pcm, d_out.p, n * sizeof(int16_t), hipMemcpyDeviceToHost));  // after the default stream's work
+    t_dtim.d2h_ms = now_ms() - t0;
+    t_dtim.total_ms += t_dtim.d2h_ms;
+    return 0;
 }
 
 }  // extern "C"

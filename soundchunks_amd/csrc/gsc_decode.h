@@ -75,4 +75,69 @@ struct Index {
 // and every validation.  0, or -1 with *err set; never reads outside [g, g + len).
 int decode_walk(const uint8_t* g, size_t len, Index* ix, std::string* err);
 
+// ---- sample ranges of resident streams (gsc_decode_crops.hip) -------------------
+// A per-channel sample position in [0, samples): the frame that contains it
+// (frames of FrameLength 0 contain nothing), the symbol row inside that frame,
+// the position inside the chunk, and the checkpoint the row's first symbol
+// belongs to.  0, or -1 with *err set.
+int index_locate(const Index& ix, int64_t sample, int* frame, int64_t* row, int* within, int64_t* checkpoint,
+                 std::string* err);
+
+// One frame of a resident stream.  Offsets index that stream's own slabs.
+struct ResFrame {
+    int64_t bs_off;        // first byte of the frame's bitstream in the byte slab
+    int64_t cb_off;        // codebook: count * cs int16
+    int64_t att_off;       // attenuations: count bytes
+    int64_t nsym;          // FrameLength * ChannelCount
+    int64_t first_sample;  // per channel
+    int64_t cp_first;      // the frame's first checkpoint
+    int32_t ver, ch, cs, count;
+    int32_t lut[32];
+};
+
+// One crop on the device: its stream's slabs and their sizes, the clipped
+// sample range, the frames [f0, f1) it crosses and its first piece.
+struct CropJob {
+    const ResFrame* frames;
+    const uint64_t* cps;
+    const uint32_t* words;
+    const int16_t* cb;
+    const uint8_t* att;
+    int64_t ncp, nwords, ncb, natt;
+    int64_t begin, count;
+    int32_t nframes, f0, f1, piece0;
+};
+
+// One frame of one crop: the checkpoint segments [seg0, seg0 + nseg) of the
+// frame are unpacked to segment slots [slot0, slot0 + nseg) of the call's
+// symbol scratch (kDecodeS words per slot).  A crop owns f1 - f0 pieces, one
+// per frame in order; an empty frame's piece has nseg 0.
+struct CropPiece {
+    int64_t slot0;
+    int64_t seg0;
+    int32_t nseg, crop, frame, pad_;
+};
+
+struct Crop {
+    int stream;
+    int64_t begin, count;
+};
+
+// The crops of one call, clipped and laid out (host only, no device needed).
+struct PlanCrop {
+    int stream;
+    int64_t begin, count;  // count clipped to the stream's end
+    int f0, f1, piece0;
+};
+struct CropPlan {
+    std::vector<PlanCrop> crops;
+    std::vector<CropPiece> pieces;
+    int64_t slots = 0;  // segment slots of the symbol scratch
+    int channels = 0;
+};
+// Refuses (-1, *err) begin < 0, begin > samples, count < 0, count > length, a
+// bad stream index and streams whose channel counts differ.
+int plan_crops(const Index* const* ixs, int nstreams, const Crop* crops, int ncrops, int64_t length, CropPlan* plan,
+               std::string* err);
+
 }  // namespace gsc

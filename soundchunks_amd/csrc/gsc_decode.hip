@@ -20,6 +20,7 @@
 #include <stdint.h>
 
 #include "gsc_decode.h"
+#include "gsc_decode_device.h"
 
 namespace gsc {
 namespace {
@@ -49,43 +50,7 @@ __global__ __launch_bounds__(kUnpackThreads) void decode_unpack_kernel(const Dec
     const int n = (int)(f.nsym - s0 < kDecodeS ? f.nsym - s0 : kDecodeS);
     const int64_t so = f.sym_off + s0;
     if (so < 0 || so + n > nsym || f.bs_off < 0) return;
-    const uint64_t cp = cps[c];
-    int hdr = (int)(cp & 7) - 1;  // variableCodingHeader on entry
-    hdr = hdr > 3 ? 3 : hdr;
-    const uint64_t bit = (cp >> 3) + (uint64_t)f.bs_off * 8;
-    int64_t w = (int64_t)(bit >> 5);
-    const int sh = (int)(bit & 31);
-    const int rev_bit = f.ver > 0 ? 1 : 0;
-    const int idx_max = f.count > 0 ? f.count - 1 : 0;
-    uint64_t buf = (w < nwords ? words[w] : 0u) >> sh;
-    int have = 32 - sh;
-    ++w;
-    uint16_t* o = sym + so;
-    for (int i = 0; i < n; ++i) {
-        if (have <= 32) {  // refill: 33 bits or more, a symbol has at most 17
-            buf |= (uint64_t)(w < nwords ? words[w] : 0u) << have;
-            have += 32;
-            ++w;
-        }
-        const uint32_t v = (uint32_t)buf;
-        const uint32_t neg = v & 1u;
-        const uint32_t rev = rev_bit ? (v >> 1) & 1u : 0u;
-        int used = 1 + rev_bit;
-        const int has = (int)((v >> used) & 1u);
-        const int nh = (int)((v >> (used + 1)) & 3u);
-        hdr = has ? nh : hdr;
-        used += 1 + 2 * has;
-        // the next four 3-bit blocks, first block most significant; the hdr + 1
-        // leading ones are the index (no per-lane trip count: lanes stay converged)
-        const uint32_t g = v >> used;
-        const uint32_t r4 = (g & 7u) << 9 | ((g >> 3) & 7u) << 6 | ((g >> 6) & 7u) << 3 | ((g >> 9) & 7u);
-        int idx = (int)(r4 >> (3 * (3 - hdr)));
-        used += 3 * (hdr + 1);
-        buf >>= used;
-        have -= used;
-        idx = idx > idx_max ? idx_max : idx;
-        o[i] = (uint16_t)((uint32_t)idx << 2 | neg << 1 | rev);
-    }
+    unpack_segment(words, nwords, f.bs_off, cps[c], f.ver, f.count, n, sym + so);
 }
 
 __global__ __launch_bounds__(kDecodeSynthThreads) void decode_synth_kernel(
@@ -128,11 +93,8 @@ __global__ __launch_bounds__(kDecodeSynthThreads) void decode_synth_kernel(
         const int64_t si = sym_base + (int64_t)q * ch + k;
         const int64_t oi = out_base + l;
         if (si < 0 || si >= nsym || oi < 0 || oi >= nout) continue;
-        const uint32_t w = sym[si];
-        int idx = (int)(w >> 2);
-        idx = idx >= count ? count - 1 : idx;
-        const int neg = (int)((w >> 1) & 1u);
-        const int jj = (w & 1u) ? cs - 1 - j : j;
+        int idx, neg, jj;
+        symbol_fields(sym[si], count, cs, j, &idx, &neg, &jj);
         int a, v;
         if (staged) {
             a = latt[idx];
@@ -144,8 +106,7 @@ __global__ __launch_bounds__(kDecodeSynthThreads) void decode_synth_kernel(
             a = att[ai];
             v = cb[ci];
         }
-        // Cardinal(attr * chunkSmp) shr 15, low word (decoder.lpr:198-201)
-        out[oi] = (int16_t)(uint16_t)(((uint32_t)(slut[neg * 16 + (a & 15)] * v)) >> 15);
+        out[oi] = synth_sample(slut[neg * 16 + (a & 15)], v);
     }
 }
 

@@ -5,6 +5,11 @@ on the MI355X.
 The host walks the stream once (``Decoder.index``: frame offsets, checkpoints,
 validation); symbols are unpacked and samples synthesised on the GPU.  There is
 no CPU fallback for the decode itself; the index needs no GPU.
+
+``Decoder.open(gsc)`` keeps a stream on the device (``ResidentStream``);
+``Decoder.decode_crops`` then decodes batches of sample ranges of such streams
+straight into a torch tensor on the device, and ``decode_samples`` one range to
+numpy.  torch is imported by ``decode_crops`` alone.
 """
 from __future__ import annotations
 
@@ -32,11 +37,12 @@ class Index:
     """The host index of one ``.gsc`` stream (``gsc_index``): per frame the
     byte offset, FrameLength, ChunkSize, ChunkCount and first sample."""
 
-    def __init__(self, gsc: bytes):
+    def __init__(self, gsc: bytes, _handle=None):
         lib = _lib.load()
         self.gsc = gsc
         self._arr, self._ptr = _u8(gsc)
-        h = lib.gsc_index_create(self._ptr, len(self._arr))
+        self._owned = _handle is None  # a resident stream's index belongs to the stream
+        h = lib.gsc_index_create(self._ptr, len(self._arr)) if _handle is None else _handle
         if not h:
             raise _lib.GscError(lib.gsc_last_error().decode(errors="replace"))
         self._h = h
@@ -63,9 +69,66 @@ class Index:
                                           ctypes.byref(pcm), ctypes.byref(n)))
         return _take(lib, pcm, n.value).reshape(-1, self.channels)
 
+    def locate(self, sample: int):
+        """(frame, symbol row, position inside the chunk, checkpoint) of a
+        per-channel sample position in [0, samples_per_channel)."""
+        fr, within = ctypes.c_int(0), ctypes.c_int(0)
+        row, cp = ctypes.c_longlong(0), ctypes.c_longlong(0)
+        _lib.check(_lib.load().gsc_index_locate(self._h, int(sample), ctypes.byref(fr), ctypes.byref(row),
+                                                ctypes.byref(within), ctypes.byref(cp)))
+        return fr.value, row.value, within.value, cp.value
+
     def close(self) -> None:
         if getattr(self, "_h", None):
-            _lib.load().gsc_index_free(self._h)
+            if self._owned:
+                _lib.load().gsc_index_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class ResidentStream:
+    """One ``.gsc`` stream kept on the device (``gsc_stream``): walked and
+    uploaded once by ``Decoder.open``; sample ranges then decode without
+    touching the bytes again (``decode_samples``, ``Decoder.decode_crops``)."""
+
+    def __init__(self, gsc: bytes):
+        lib = _lib.load()
+        arr, ptr = _u8(gsc)
+        h = lib.gsc_stream_open(ptr, len(arr))
+        if not h:
+            raise _lib.GscError(lib.gsc_last_error().decode(errors="replace"))
+        self._h = h
+        ch, sr, ns, nf = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_longlong(0), ctypes.c_int(0)
+        _lib.check(lib.gsc_stream_info(h, ctypes.byref(ch), ctypes.byref(sr), ctypes.byref(ns), ctypes.byref(nf)))
+        self.channels, self.sample_rate, self.samples_per_channel, self.frame_count = (ch.value, sr.value, ns.value,
+                                                                                       nf.value)
+        self.device = lib.gsc_stream_device(h)
+        self.index = Index(gsc, _handle=lib.gsc_stream_index(h))
+
+    def decode_samples(self, begin: int, end: int) -> np.ndarray:
+        """Samples [begin, end) -> int16 array [end - begin, channels] on the host."""
+        n = int(end) - int(begin)
+        if n < 0:
+            raise _lib.GscError(f"decode_samples: end {end} < begin {begin}")
+        out = np.zeros((n, self.channels), np.int16)
+        _lib.check(_lib.load().gsc_stream_decode_samples(self._handle(), int(begin), n,
+                                                         out.ctypes.data_as(ctypes.POINTER(ctypes.c_int16))))
+        return out
+
+    def _handle(self):
+        if not getattr(self, "_h", None):
+            raise _lib.GscError("the resident stream is closed")
+        return self._h
+
+    def close(self) -> None:
+        if getattr(self, "_h", None):
+            self.index.close()
+            _lib.load().gsc_stream_free(self._h)
             self._h = None
 
     def __del__(self):
@@ -91,6 +154,67 @@ class Decoder:
     @staticmethod
     def checkpoint_symbols() -> int:
         return _lib.load().gsc_decode_checkpoint_symbols()
+
+    @staticmethod
+    def open(gsc: bytes) -> ResidentStream:
+        return ResidentStream(gsc)
+
+    CROP_VARIANTS = ("global", "lds", "fused")
+
+    @staticmethod
+    def crop_variant(name=None) -> str:
+        """Measurement knob, not a stable interface (``gsc_decode_crops_variant``):
+        how this thread's crop calls run.  "global": unpack, then synthesis with
+        the codebook read from global memory; "lds": the same with the codebook
+        staged in LDS; "fused" (the default): one launch, symbols through LDS.
+        Returns the previous setting; ``None`` only queries.  Same output."""
+        v = -1 if name is None else Decoder.CROP_VARIANTS.index(name)
+        return Decoder.CROP_VARIANTS[_lib.load().gsc_decode_crops_variant(v)]
+
+    @staticmethod
+    def decode_crops(streams, crops, length: int, dtype=None, layout: str = "TC", out=None):
+        """``crops``: (stream index, begin, count) in per-channel samples.
+        Returns (tensor on the streams' device, [B, length, C] for layout "TC"
+        or [B, C, length] for "CT", int16 or float32 = int16 / 32768; written
+        lengths).  Crop i fills row i, clipped at its stream's end, zero after.
+        The work is enqueued on torch's current stream; nothing is synchronised."""
+        import torch
+
+        lib = _lib.load()
+        streams, crops = list(streams), [tuple(int(v) for v in c) for c in crops]
+        if not streams:
+            raise _lib.GscError("decode_crops: no streams")
+        dtype = torch.int16 if dtype is None else dtype
+        if dtype not in (torch.int16, torch.float32):
+            raise _lib.GscError(f"decode_crops: dtype {dtype} is neither torch.int16 nor torch.float32")
+        if layout not in ("TC", "CT"):
+            raise _lib.GscError(f"decode_crops: layout {layout!r} is neither 'TC' nor 'CT'")
+        length = int(length)
+        if length < 0:
+            raise _lib.GscError(f"decode_crops: length {length}")
+        ch = streams[0].channels
+        device = torch.device("cuda", streams[0].device)
+        shape = (len(crops), length, ch) if layout == "TC" else (len(crops), ch, length)
+        if out is None:
+            out = torch.empty(shape, dtype=dtype, device=device)
+        else:
+            if out.device != device:
+                raise _lib.GscError(f"decode_crops: out is on {out.device}, the streams live on {device}")
+            if out.dtype != dtype or tuple(out.shape) != shape or not out.is_contiguous():
+                raise _lib.GscError(f"decode_crops: out must be a contiguous {dtype} tensor of shape {shape}, got "
+                                    f"{out.dtype} {tuple(out.shape)}")
+        # an empty tensor has no memory: the library still checks the crops, and writes nothing
+        dst = out if out.numel() else torch.empty(1, dtype=dtype, device=device)
+        hs = (ctypes.c_void_p * len(streams))(*[s._handle() for s in streams])
+        cr = (_lib.GscCrop * max(1, len(crops)))(*[_lib.GscCrop(*c) for c in crops])
+        written = (ctypes.c_longlong * max(1, len(crops)))()
+        with torch.cuda.device(device):
+            _lib.check(lib.gsc_decode_crops(hs, len(streams), cr, len(crops),
+                                            _lib.PCM_FLOAT32 if dtype == torch.float32 else _lib.PCM_INT16,
+                                            _lib.LAYOUT_CT if layout == "CT" else _lib.LAYOUT_TC, length,
+                                            dst.data_ptr(),
+                                            ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream), written))
+        return out, [int(written[i]) for i in range(len(crops))]
 
     def decode(self, gsc: bytes, frame_begin: int = 0, frame_end: int = -1):
         """(int16 array [n, channels], sample_rate) of frames [frame_begin, frame_end)."""
