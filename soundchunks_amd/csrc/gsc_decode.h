@@ -1,6 +1,7 @@
-// .gsc decoder: the host index of a stream and the device
-// descriptors of its unpack and synthesis kernels (gsc_decode.cpp,
-// gsc_decode.hip).  The format is decoder/decoder.lpr:37-220.
+// .gsc decoder: the host index of a stream
+// (gsc_decode_index.cpp) and the device descriptors of the unpack and
+// synthesis kernels (gsc_decode.hip, gsc_decode_crops.hip), which
+// gsc_decode_abi.cpp fills.  The format is decoder/decoder.lpr:37-220.
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -21,18 +22,32 @@ constexpr int kDecodeS = GSC_DECODE_S;
 constexpr int kDecodeLdsBytes = 136 * 1024;
 constexpr int kDecodeSynthThreads = 1024;
 
-// One frame on the device.  Offsets index the slabs of one decode call.
-struct DecFrame {
+// A frame's tables as a synthesis workgroup stages them in LDS: the codebook
+// (int16), the attenuations (bytes) from the next whole word on, `bytes` in all.
+struct StagedSize {
+    int64_t att_at, bytes;
+};
+constexpr StagedSize staged_size(int64_t count, int64_t cs) {
+    const int64_t att_at = (count * cs * 2 + 3) & ~int64_t(3);
+    return StagedSize{att_at, att_at + count};
+}
+
+// What every kernel needs of one frame.  Offsets index the slabs the frame
+// was uploaded to: those of one decode call, or a resident stream's own.
+struct FrameTables {
     int64_t bs_off;    // first byte of the frame's bitstream in the byte slab
-    int64_t sym_off;   // first symbol word (idx << 2 | neg << 1 | rev) of the frame
-    int64_t out_off;   // first int16 of the frame in the output, interleaved [sample][channel]
     int64_t cb_off;    // codebook: count * cs int16 (a multiple of 8 elements)
     int64_t att_off;   // attenuations: count bytes
     int64_t nsym;      // FrameLength * ChannelCount
-    int32_t cp_first;  // the frame's first checkpoint
+    int64_t cp_first;  // the frame's first checkpoint
     int32_t ver, ch, cs, count;
-    int32_t pad_;
     int32_t lut[32];   // CAttrLookup[negative][attenuation] (decoder.lpr:88-96)
+};
+
+// One frame of a whole-frame decode call.
+struct DecFrame : FrameTables {
+    int64_t sym_off;  // first symbol word (idx << 2 | neg << 1 | rev) of the frame
+    int64_t out_off;  // first int16 of the frame in the output, interleaved [sample][channel]
 };
 
 // One synthesis workgroup's share of a frame: symbol rows [row0, row0 + rows),
@@ -83,16 +98,9 @@ int decode_walk(const uint8_t* g, size_t len, Index* ix, std::string* err);
 int index_locate(const Index& ix, int64_t sample, int* frame, int64_t* row, int* within, int64_t* checkpoint,
                  std::string* err);
 
-// One frame of a resident stream.  Offsets index that stream's own slabs.
-struct ResFrame {
-    int64_t bs_off;        // first byte of the frame's bitstream in the byte slab
-    int64_t cb_off;        // codebook: count * cs int16
-    int64_t att_off;       // attenuations: count bytes
-    int64_t nsym;          // FrameLength * ChannelCount
+// One frame of a resident stream.
+struct ResFrame : FrameTables {
     int64_t first_sample;  // per channel
-    int64_t cp_first;      // the frame's first checkpoint
-    int32_t ver, ch, cs, count;
-    int32_t lut[32];
 };
 
 // One crop on the device: its stream's slabs and their sizes, the clipped

@@ -1,6 +1,6 @@
 // .gsc decode on MI355X (gfx950): SURVEY.md §8 f5, decoder/decoder.lpr:163-203.
 //
-//   decode_unpack_kernel  one lane per checkpoint segment (gsc_decode.cpp's
+//   decode_unpack_kernel  one lane per checkpoint segment (gsc_decode_index.cpp's
 //                         walk leaves a checkpoint every kDecodeS symbols):
 //                         reads the segment's bits from the compressed bytes
 //                         and writes one u16 word per symbol,
@@ -35,16 +35,7 @@ __global__ __launch_bounds__(kUnpackThreads) void decode_unpack_kernel(const Dec
     const int64_t c = (int64_t)blockIdx.x * kUnpackThreads + threadIdx.x;
     if (c >= ncp) return;
     // the last frame whose first checkpoint is <= c (empty frames own none)
-    int lo = 0, hi = nframes - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (frames[mid].cp_first <= c) {
-            lo = mid;
-        } else {
-            hi = mid - 1;
-        }
-    }
-    const DecFrame& f = frames[lo];
+    const DecFrame& f = frames[last_le(0, nframes - 1, c, [&](int i) { return frames[i].cp_first; })];
     const int64_t s0 = (c - f.cp_first) * kDecodeS;
     if (s0 < 0 || s0 >= f.nsym) return;
     const int n = (int)(f.nsym - s0 < kDecodeS ? f.nsym - s0 : kDecodeS);
@@ -63,26 +54,15 @@ __global__ __launch_bounds__(kDecodeSynthThreads) void decode_synth_kernel(
     const DecJob job = jobs[blockIdx.x];
     if (job.frame < 0 || job.frame >= nframes) return;
     const DecFrame& f = frames[job.frame];
-    const int cs = f.cs, ch = f.ch, count = f.count;
-    if (cs <= 0 || ch <= 0 || count <= 0 || job.rows <= 0 || job.row0 < 0) return;
+    const int cs = f.cs, ch = f.ch;
+    if (cs <= 0 || ch <= 0 || f.count <= 0 || job.rows <= 0 || job.row0 < 0) return;
     const int row = cs * ch;
     if ((int64_t)job.rows * row > ((int64_t)1 << 30)) return;
     const int tid = threadIdx.x;
     if (tid < 32) slut[tid] = f.lut[tid];
     // the frame's codebook and attenuations in LDS when they fit
-    const int64_t cbn = (int64_t)count * cs;
-    const int64_t att_at = (cbn * 2 + 3) & ~(int64_t)3;
-    const bool staged = att_at + count <= lds_bytes && f.cb_off >= 0 && (f.cb_off & 1) == 0 &&
-                        f.cb_off + cbn + 1 <= ncb && f.att_off >= 0 && f.att_off + count <= natt;
-    const int16_t* lcb = reinterpret_cast<const int16_t*>(smem);
-    const uint8_t* latt = smem + att_at;
-    if (staged) {
-        const uint32_t* src = reinterpret_cast<const uint32_t*>(cb + f.cb_off);
-        uint32_t* dst = reinterpret_cast<uint32_t*>(smem);
-        const int nw = (int)((cbn + 1) / 2);
-        for (int i = tid; i < nw; i += kDecodeSynthThreads) dst[i] = src[i];
-        for (int i = tid; i < count; i += kDecodeSynthThreads) smem[att_at + i] = att[f.att_off + i];
-    }
+    const TableSlabs g{cb, ncb, att, natt};
+    const StagedTables lds = stage_tables(f, g, lds_bytes, smem, tid, kDecodeSynthThreads);
     __syncthreads();
     const int total = job.rows * row;
     const int64_t sym_base = f.sym_off + job.row0 * ch;
@@ -93,20 +73,7 @@ __global__ __launch_bounds__(kDecodeSynthThreads) void decode_synth_kernel(
         const int64_t si = sym_base + (int64_t)q * ch + k;
         const int64_t oi = out_base + l;
         if (si < 0 || si >= nsym || oi < 0 || oi >= nout) continue;
-        int idx, neg, jj;
-        symbol_fields(sym[si], count, cs, j, &idx, &neg, &jj);
-        int a, v;
-        if (staged) {
-            a = latt[idx];
-            v = lcb[idx * cs + jj];
-        } else {
-            int64_t ai = f.att_off + idx, ci = f.cb_off + (int64_t)idx * cs + jj;
-            ai = ai < 0 ? 0 : (ai >= natt ? natt - 1 : ai);
-            ci = ci < 0 ? 0 : (ci >= ncb ? ncb - 1 : ci);
-            a = att[ai];
-            v = cb[ci];
-        }
-        out[oi] = synth_sample(slut[neg * 16 + (a & 15)], v);
+        out[oi] = table_sample(f, slut, sym[si], j, lds, g);
     }
 }
 
@@ -131,11 +98,9 @@ extern "C" hipError_t gsc_launch_decode_synth(const DecFrame* frames, int nframe
                                               hipStream_t st) {
     if (nframes <= 0 || njobs <= 0) return hipSuccess;
     if (lds_bytes < 0 || lds_bytes > kDecodeLdsBytes) return hipErrorInvalidValue;
-    if (lds_bytes > 32 * 1024) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(decode_synth_kernel),
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
-        if (e != hipSuccess) return e;
-    }
+    static LdsLimit lim;
+    const hipError_t e = allow_lds(decode_synth_kernel, lds_bytes, &lim);
+    if (e != hipSuccess) return e;
     hipLaunchKernelGGL(decode_synth_kernel, dim3((unsigned)njobs), dim3(kDecodeSynthThreads), (size_t)lds_bytes, st,
                        frames, nframes, jobs, njobs, lds_bytes, sym, nsym, cb, ncb, att, natt, out, nout);
     return hipGetLastError();

@@ -1,0 +1,598 @@
+// .gsc decoder, HIP runtime side and C ABI.
+//
+// decode_parts uploads the frames a call asks for, as gsc_decode_index.cpp's
+// walk indexed them, and runs gsc_decode.hip's two stages over all of them.  A
+// resident stream (gsc_stream_open) keeps the index and the bytes on the
+// device; gsc_decode_crops then decodes batches of sample ranges into
+// caller-owned device memory (plan_crops; gsc_decode_crops.hip).  Both keep
+// their device copies in a Slabs and describe a frame with frame_tables.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <chrono>
+#include <cstdlib>
+#include <cstring>
+#include <memory>
+
+#include "../../include/soundchunks.h"
+#include "gsc_decode.h"
+#include "gsc_device.h"
+
+extern "C" hipError_t gsc_launch_decode_unpack(const gsc::DecFrame* frames, int nframes, const uint64_t* cps,
+                                               int64_t ncp, const uint32_t* words, int64_t nwords, uint16_t* sym,
+                                               int64_t nsym, hipStream_t st);
+extern "C" hipError_t gsc_launch_decode_synth(const gsc::DecFrame* frames, int nframes, const gsc::DecJob* jobs,
+                                              int njobs, int lds_bytes, const uint16_t* sym, int64_t nsym,
+                                              const int16_t* cb, int64_t ncb, const uint8_t* att, int64_t natt,
+                                              int16_t* out, int64_t nout, hipStream_t st);
+
+extern "C" hipError_t gsc_launch_crop_unpack(const gsc::CropJob* jobs, int ncrops, const gsc::CropPiece* pieces,
+                                             int npieces, uint16_t* sym, int64_t nslots, hipStream_t st);
+extern "C" hipError_t gsc_launch_crop_synth(const gsc::CropJob* jobs, int ncrops, const gsc::CropPiece* pieces,
+                                            int npieces, const uint16_t* sym, int64_t nslots, int64_t length,
+                                            int channels, int is_float, int planar, int lds_bytes, int tile_len,
+                                            void* out, hipStream_t st);
+extern "C" hipError_t gsc_launch_crop_fused(const gsc::CropJob* jobs, int ncrops, int64_t length, int channels,
+                                            int is_float, int planar, int tile_len, void* out, hipStream_t st);
+
+struct gsc_index {
+    gsc::Index ix;
+};
+
+namespace gsc {
+
+int set_last_error(const std::string& m);
+int require_device();
+
+namespace {
+
+thread_local gsc_decode_timing t_dtim;
+// crop decode: 0 unpack, then synthesis with the codebook from global memory; 1 the same with the codebook
+// staged in LDS; 2 unpack and synthesis fused in one launch (DESIGN.md "f5 decoder" has the A/B)
+thread_local int t_crop_variant = 2;
+
+double now_ms() {
+    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
+}
+
+#define DEC_TRY(expr)                                                                                 \
+    do {                                                                                              \
+        hipError_t e_ = (expr);                                                                       \
+        if (e_ != hipSuccess) return set_last_error(std::string(#expr) + ": " + hipGetErrorString(e_)); \
+    } while (0)
+
+template <typename T>
+struct Dev {
+    T* p = nullptr;
+    ~Dev() {
+        if (p) (void)hipFree(p);
+    }
+    hipError_t alloc(size_t n) { return hipMalloc(reinterpret_cast<void**>(&p), sizeof(T) * std::max<size_t>(n, 1)); }
+};
+
+struct Event {
+    hipEvent_t e = nullptr;
+    ~Event() {
+        if (e) (void)hipEventDestroy(e);
+    }
+};
+
+// A position in, or a length of, each of the four slabs: stream bytes,
+// checkpoints, codebook int16 and attenuation bytes.
+struct SlabPos {
+    int64_t bytes = 0, cps = 0, cb = 0, att = 0;
+};
+SlabPos operator+(const SlabPos& a, const SlabPos& b) {
+    return {a.bytes + b.bytes, a.cps + b.cps, a.cb + b.cb, a.att + b.att};
+}
+SlabPos operator-(const SlabPos& a, const SlabPos& b) {
+    return {a.bytes - b.bytes, a.cps - b.cps, a.cb - b.cb, a.att - b.att};
+}
+
+// What frames [b, e) of a stream occupy of its bytes and of its index's arrays.
+struct Span {
+    SlabPos first, count;
+};
+Span span_of(const Index& ix, int b, int e) {
+    if (b >= e) return Span{};
+    const IndexFrame& fb = ix.frames[size_t(b)];
+    const IndexFrame& fe = ix.frames[size_t(e) - 1];
+    const SlabPos first{int64_t(fb.off), int64_t(fb.cp_first), int64_t(fb.cb_first), int64_t(fb.att_first)};
+    const SlabPos end{int64_t(fe.end_off), int64_t(fe.cp_first + fe.cp_count),
+                      int64_t(fe.cb_first + ((size_t(fe.count) * size_t(fe.cs) + 7) & ~size_t(7))),
+                      int64_t(fe.att_first + size_t(fe.count))};
+    return Span{first, end - first};
+}
+
+// The device descriptor of a frame whose stream was uploaded so that position
+// p of the stream lies at rebase + p of the slabs.
+FrameTables frame_tables(const IndexFrame& f, const SlabPos& rebase) {
+    FrameTables d{};
+    d.bs_off = rebase.bytes + int64_t(f.bs_off);
+    d.cb_off = rebase.cb + int64_t(f.cb_first);
+    d.att_off = rebase.att + int64_t(f.att_first);
+    d.nsym = f.nsym;
+    d.cp_first = rebase.cps + int64_t(f.cp_first);
+    d.ver = f.ver;
+    d.ch = f.ch;
+    d.cs = f.cs;
+    d.count = f.count;
+    std::memcpy(d.lut, f.lut, sizeof(d.lut));
+    return d;
+}
+
+// the dynamic LDS a synthesis workgroup wants for a frame: its staged tables when they fit
+int frame_lds_bytes(const IndexFrame& f) {
+    const int64_t need = staged_size(f.count, f.cs).bytes;
+    return f.flen > 0 && need <= kDecodeLdsBytes ? int(need) : 0;
+}
+
+// The device copy of one or more spans and of their frame table, freed with
+// the owner.  The byte slab is whole words plus 16 zero bytes, the codebook
+// ends in 16 zero int16 and the attenuations in one zero byte; nwords, ncp,
+// ncb and natt are what a kernel may index, those tails included.
+template <typename Frame>
+struct Slabs {
+    Dev<uint8_t> bytes, att;
+    Dev<uint64_t> cps;
+    Dev<int16_t> cb;
+    Dev<Frame> frames;
+    int64_t nwords = 0, ncp = 0, ncb = 0, natt = 0;
+    long long h2d_bytes = 0;  // what put and put_frames copied
+
+    const uint32_t* words() const { return reinterpret_cast<const uint32_t*>(bytes.p); }
+
+    int alloc(const SlabPos& n, size_t nframes) {
+        const size_t whole = size_t(n.bytes) & ~size_t(3), byte_alloc = ((size_t(n.bytes) + 3) & ~size_t(3)) + 16;
+        nwords = int64_t(byte_alloc / 4);
+        ncp = n.cps;
+        ncb = n.cb + 16;
+        natt = n.att + 1;
+        DEC_TRY(bytes.alloc(byte_alloc));
+        DEC_TRY(att.alloc(size_t(natt)));
+        DEC_TRY(cps.alloc(size_t(ncp)));
+        DEC_TRY(cb.alloc(size_t(ncb)));
+        DEC_TRY(frames.alloc(nframes));
+        DEC_TRY(hipMemset(bytes.p + whole, 0, byte_alloc - whole));
+        DEC_TRY(hipMemset(cb.p + n.cb, 0, 16 * sizeof(int16_t)));
+        DEC_TRY(hipMemset(att.p + n.att, 0, 1));
+        return 0;
+    }
+    // span sp of stream g, indexed by ix, to position `at` of the slabs
+    int put(const Span& sp, const SlabPos& at, const uint8_t* g, const Index& ix) {
+        const SlabPos &a = sp.first, &n = sp.count;
+        if (n.bytes) DEC_TRY(hipMemcpy(bytes.p + at.bytes, g + a.bytes, size_t(n.bytes), hipMemcpyHostToDevice));
+        if (n.cps)
+            DEC_TRY(hipMemcpy(cps.p + at.cps, ix.cps.data() + a.cps, size_t(n.cps) * sizeof(uint64_t),
+                              hipMemcpyHostToDevice));
+        if (n.cb)
+            DEC_TRY(hipMemcpy(cb.p + at.cb, ix.codebook.data() + a.cb, size_t(n.cb) * sizeof(int16_t),
+                              hipMemcpyHostToDevice));
+        if (n.att) DEC_TRY(hipMemcpy(att.p + at.att, ix.att.data() + a.att, size_t(n.att), hipMemcpyHostToDevice));
+        h2d_bytes += n.bytes + n.cps * int64_t(sizeof(uint64_t)) + n.cb * int64_t(sizeof(int16_t)) + n.att;
+        return 0;
+    }
+    int put_frames(const std::vector<Frame>& f) {
+        DEC_TRY(hipMemcpy(frames.p, f.data(), f.size() * sizeof(Frame), hipMemcpyHostToDevice));
+        h2d_bytes += (long long)(f.size() * sizeof(Frame));
+        return 0;
+    }
+};
+
+// frames [b, e) of one stream
+struct Part {
+    const uint8_t* g;
+    const Index* ix;
+    int b, e;
+};
+
+void clamp_range(const Index& ix, int* b, int* e) {
+    const int n = int(ix.frames.size());
+    *b = std::max(*b, 0);
+    *e = *e < 0 ? n : std::min(*e, n);
+    if (*e < *b) *e = *b;
+}
+
+// Every frame of every part in one launch per stage.  *pcm: the parts' samples
+// back to back (malloc), part_values[i] int16 values each.
+int decode_parts(const std::vector<Part>& parts, int16_t** pcm, size_t* pcm_len, size_t* part_values,
+                 gsc_decode_timing* tim) {
+    const double t_begin = now_ms();
+    std::vector<DecFrame> frames;
+    std::vector<DecJob> jobs;
+    std::vector<Span> spans(parts.size());
+    std::vector<SlabPos> bases(parts.size());
+    SlabPos total;  // cb: a multiple of 8, as every cb_first
+    int64_t nsym = 0, nout = 0;
+    int lds_bytes = 0;
+    for (size_t pi = 0; pi < parts.size(); ++pi) {
+        const Part& pt = parts[pi];
+        const Span& sp = spans[pi] = span_of(*pt.ix, pt.b, pt.e);
+        bases[pi] = total;
+        total = total + sp.count;
+        const int64_t out_before = nout;
+        for (int i = pt.b; i < pt.e; ++i) {
+            const IndexFrame& f = pt.ix->frames[size_t(i)];
+            DecFrame d{};
+            static_cast<FrameTables&>(d) = frame_tables(f, bases[pi] - sp.first);
+            d.sym_off = nsym;
+            d.out_off = nout;
+            const int64_t row = int64_t(f.cs) * f.ch;  // int16 values per symbol row
+            const int64_t cbn = int64_t(f.count) * f.cs;
+            if (f.flen > 0) {
+                lds_bytes = std::max(lds_bytes, frame_lds_bytes(f));
+                // a workgroup stages the codebook once: give it at least 4 codebooks' worth of output
+                const int64_t target = std::min<int64_t>(std::max<int64_t>(4 * cbn, 64 * 1024), int64_t(1) << 30);
+                const int64_t rows_per = std::max<int64_t>(1, target / row);
+                for (int64_t r = 0; r < int64_t(f.flen); r += rows_per)
+                    jobs.push_back(DecJob{r, int32_t(std::min<int64_t>(rows_per, int64_t(f.flen) - r)),
+                                          int32_t(frames.size())});
+            }
+            nsym += f.nsym;
+            nout += int64_t(f.flen) * row;
+            frames.push_back(d);
+        }
+        if (part_values) part_values[pi] = size_t(nout - out_before);
+    }
+    if (total.cps >= (int64_t(1) << 31) || frames.size() >= (size_t(1) << 31) || jobs.size() >= (size_t(1) << 31))
+        return set_last_error("gsc decode: stream too large for one call");
+    int16_t* host_out = static_cast<int16_t*>(std::malloc(std::max<size_t>(size_t(nout) * 2, 2)));
+    if (!host_out) return set_last_error("gsc decode: out of memory");
+    struct FreeOnFail {
+        int16_t* p;
+        ~FreeOnFail() { std::free(p); }
+    } guard{host_out};
+    tim->frames = int(frames.size());
+    tim->symbols = nsym;
+    tim->samples = nout;
+    if (nout > 0) {
+        if (require_device() != 0) return -1;
+        Slabs<DecFrame> s;
+        Dev<DecJob> d_jobs;
+        Dev<int16_t> d_out;
+        Dev<uint16_t> d_sym;
+        Event e0, e1, e2;
+        const double t0 = now_ms();
+        if (s.alloc(total, frames.size()) != 0) return -1;
+        DEC_TRY(d_jobs.alloc(jobs.size()));
+        DEC_TRY(d_out.alloc(size_t(nout)));
+        DEC_TRY(d_sym.alloc(size_t(nsym)));
+        DEC_TRY(hipEventCreate(&e0.e));
+        DEC_TRY(hipEventCreate(&e1.e));
+        DEC_TRY(hipEventCreate(&e2.e));
+        for (size_t pi = 0; pi < parts.size(); ++pi)
+            if (s.put(spans[pi], bases[pi], parts[pi].g, *parts[pi].ix) != 0) return -1;
+        if (s.put_frames(frames) != 0) return -1;
+        DEC_TRY(hipMemcpy(d_jobs.p, jobs.data(), jobs.size() * sizeof(DecJob), hipMemcpyHostToDevice));
+        DEC_TRY(hipDeviceSynchronize());
+        tim->h2d_bytes = s.h2d_bytes + (long long)(jobs.size() * sizeof(DecJob));
+        const double t1 = now_ms();
+        DEC_TRY(hipEventRecord(e0.e, nullptr));
+        DEC_TRY(gsc_launch_decode_unpack(s.frames.p, int(frames.size()), s.cps.p, s.ncp, s.words(), s.nwords, d_sym.p,
+                                         nsym, nullptr));
+        DEC_TRY(hipEventRecord(e1.e, nullptr));
+        DEC_TRY(gsc_launch_decode_synth(s.frames.p, int(frames.size()), d_jobs.p, int(jobs.size()), lds_bytes, d_sym.p,
+                                        nsym, s.cb.p, s.ncb, s.att.p, s.natt, d_out.p, nout, nullptr));
+        DEC_TRY(hipEventRecord(e2.e, nullptr));
+        DEC_TRY(hipEventSynchronize(e2.e));
+        float ms_u = 0, ms_s = 0;
+        DEC_TRY(hipEventElapsedTime(&ms_u, e0.e, e1.e));
+        DEC_TRY(hipEventElapsedTime(&ms_s, e1.e, e2.e));
+        const double t2 = now_ms();
+        DEC_TRY(hipMemcpy(host_out, d_out.p, size_t(nout) * 2, hipMemcpyDeviceToHost));
+        tim->h2d_ms = t1 - t0;
+        tim->gpu_unpack_ms = ms_u;
+        tim->gpu_synth_ms = ms_s;
+        tim->d2h_ms = now_ms() - t2;
+    }
+    guard.p = nullptr;
+    *pcm = host_out;
+    *pcm_len = size_t(nout);
+    tim->total_ms += now_ms() - t_begin;
+    return 0;
+}
+
+}  // namespace
+}  // namespace gsc
+
+// A stream resident on one device: the index, and on the device its slabs
+// (every byte, every checkpoint, the int16 codebooks, the attenuations and
+// the frame table), until gsc_stream_free.
+struct gsc_stream {
+    gsc_index idx;
+    int device = 0;
+    int lds_bytes = 0;  // the largest staged codebook + attenuations of a frame
+    gsc::Slabs<gsc::ResFrame> slabs;
+};
+
+using namespace gsc;
+
+extern "C" {
+
+gsc_index* gsc_index_create(const uint8_t* gsc, size_t len) {
+    gsc_index* h = new gsc_index();
+    std::string err;
+    if (decode_walk(gsc, len, &h->ix, &err) != 0) {
+        delete h;
+        set_last_error(err);
+        return nullptr;
+    }
+    return h;
+}
+
+int gsc_index_frame_count(const gsc_index* ix) { return ix ? int(ix->ix.frames.size()) : set_last_error("null index"); }
+
+int gsc_index_info(const gsc_index* ix, int* channels, int* sample_rate, long long* samples_per_channel) {
+    if (!ix) return set_last_error("null index");
+    if (channels) *channels = ix->ix.channels;
+    if (sample_rate) *sample_rate = ix->ix.rate;
+    if (samples_per_channel) *samples_per_channel = ix->ix.samples;
+    return 0;
+}
+
+int gsc_index_frames(const gsc_index* ix, size_t* byte_offset, int* frame_length, int* chunk_size, int* chunk_count,
+                     long long* first_sample) {
+    if (!ix) return set_last_error("null index");
+    const auto& fr = ix->ix.frames;
+    for (size_t i = 0; i < fr.size(); ++i) {
+        if (byte_offset) byte_offset[i] = fr[i].off;
+        if (frame_length) frame_length[i] = int(fr[i].flen);
+        if (chunk_size) chunk_size[i] = fr[i].cs;
+        if (chunk_count) chunk_count[i] = fr[i].count;
+        if (first_sample) first_sample[i] = fr[i].first_sample;
+    }
+    if (byte_offset) byte_offset[fr.size()] = ix->ix.len;
+    if (first_sample) first_sample[fr.size()] = ix->ix.samples;
+    return 0;
+}
+
+void gsc_index_free(gsc_index* ix) { delete ix; }
+
+int gsc_decode_checkpoint_symbols(void) { return kDecodeS; }
+
+int gsc_decode_indexed(const uint8_t* gsc, size_t len, const gsc_index* ix, int frame_begin, int frame_end,
+                       int16_t** pcm, size_t* pcm_len) {
+    if (!gsc || !ix || !pcm || !pcm_len) return set_last_error("gsc_decode_indexed: invalid argument");
+    if (len != ix->ix.len) return set_last_error("gsc_decode_indexed: the index was built from another stream");
+    t_dtim = gsc_decode_timing{};
+    Part pt{gsc, &ix->ix, frame_begin, frame_end};
+    clamp_range(ix->ix, &pt.b, &pt.e);
+    return decode_parts({pt}, pcm, pcm_len, nullptr, &t_dtim);
+}
+
+int gsc_decode(const uint8_t* gsc, size_t len, int16_t** pcm, size_t* pcm_len, int* channels, int* sample_rate) {
+    if (!pcm || !pcm_len) return set_last_error("gsc_decode: invalid argument");
+    t_dtim = gsc_decode_timing{};
+    const double t0 = now_ms();
+    Index ix;
+    std::string err;
+    if (decode_walk(gsc, len, &ix, &err) != 0) return set_last_error(err);
+    t_dtim.host_index_ms = now_ms() - t0;
+    t_dtim.total_ms = t_dtim.host_index_ms;
+    if (channels) *channels = ix.channels;
+    if (sample_rate) *sample_rate = ix.rate;
+    return decode_parts({Part{gsc, &ix, 0, int(ix.frames.size())}}, pcm, pcm_len, nullptr, &t_dtim);
+}
+
+int gsc_decode_many(const uint8_t* const* gscs, const size_t* lens, int file_count, int16_t** pcm,
+                    size_t* file_samples, int* channels, int* sample_rate) {
+    if (!gscs || !lens || file_count <= 0 || !pcm || !file_samples)
+        return set_last_error("gsc_decode_many: invalid argument");
+    t_dtim = gsc_decode_timing{};
+    const double t0 = now_ms();
+    std::vector<Index> ixs(static_cast<size_t>(file_count));
+    std::vector<Part> parts;
+    for (int i = 0; i < file_count; ++i) {
+        std::string err;
+        if (decode_walk(gscs[i], lens[i], &ixs[size_t(i)], &err) != 0)
+            return set_last_error("file " + std::to_string(i) + ": " + err);
+        if (ixs[size_t(i)].channels != ixs[0].channels || ixs[size_t(i)].rate != ixs[0].rate)
+            return set_last_error("gsc_decode_many: file " + std::to_string(i) +
+                                  " differs from file 0 in ChannelCount / SampleRate");
+        parts.push_back(Part{gscs[i], &ixs[size_t(i)], 0, int(ixs[size_t(i)].frames.size())});
+    }
+    t_dtim.host_index_ms = now_ms() - t0;
+    t_dtim.total_ms = t_dtim.host_index_ms;
+    if (channels) *channels = ixs[0].channels;
+    if (sample_rate) *sample_rate = ixs[0].rate;
+    size_t total = 0;
+    return decode_parts(parts, pcm, &total, file_samples, &t_dtim);
+}
+
+void gsc_last_decode_timing(gsc_decode_timing* t) {
+    if (t) *t = t_dtim;
+}
+
+int gsc_index_locate(const gsc_index* ix, long long sample, int* frame, long long* row, int* within,
+                     long long* checkpoint) {
+    if (!ix) return set_last_error("null index");
+    std::string err;
+    int64_t r = 0, c = 0;
+    if (index_locate(ix->ix, sample, frame, &r, within, &c, &err) != 0) return set_last_error(err);
+    if (row) *row = r;
+    if (checkpoint) *checkpoint = c;
+    return 0;
+}
+
+void gsc_stream_free(gsc_stream* st) {
+    if (!st) return;
+    int cur = 0;
+    const bool sw = hipGetDevice(&cur) == hipSuccess && cur != st->device;
+    if (sw) (void)hipSetDevice(st->device);
+    (void)hipDeviceSynchronize();  // queued crop decodes still read the slabs
+    delete st;
+    if (sw) (void)hipSetDevice(cur);
+}
+
+static int stream_open(const uint8_t* gsc, size_t len, gsc_stream* h) {
+    const double t0 = now_ms();
+    std::string err;
+    if (decode_walk(gsc, len, &h->idx.ix, &err) != 0) return set_last_error(err);
+    const Index& ix = h->idx.ix;
+    t_dtim.host_index_ms = now_ms() - t0;
+    if (require_device() != 0) return -1;
+    DEC_TRY(hipGetDevice(&h->device));
+    std::vector<ResFrame> frames(ix.frames.size());
+    for (size_t i = 0; i < frames.size(); ++i) {
+        const IndexFrame& f = ix.frames[i];
+        static_cast<FrameTables&>(frames[i]) = frame_tables(f, SlabPos{});
+        frames[i].first_sample = f.first_sample;
+        h->lds_bytes = std::max(h->lds_bytes, frame_lds_bytes(f));
+    }
+    const double t1 = now_ms();
+    const Span all = span_of(ix, 0, int(frames.size()));  // the whole stream, at position 0
+    if (h->slabs.alloc(all.count, frames.size()) != 0 || h->slabs.put(all, SlabPos{}, gsc, ix) != 0 ||
+        h->slabs.put_frames(frames) != 0)
+        return -1;
+    DEC_TRY(hipDeviceSynchronize());
+    t_dtim.h2d_ms = now_ms() - t1;
+    t_dtim.h2d_bytes = h->slabs.h2d_bytes;
+    t_dtim.frames = int(frames.size());
+    t_dtim.total_ms = now_ms() - t0;
+    return 0;
+}
+
+gsc_stream* gsc_stream_open(const uint8_t* gsc, size_t len) {
+    t_dtim = gsc_decode_timing{};
+    std::unique_ptr<gsc_stream> h(new gsc_stream());
+    return stream_open(gsc, len, h.get()) == 0 ? h.release() : nullptr;
+}
+
+int gsc_stream_info(const gsc_stream* st, int* channels, int* sample_rate, long long* samples_per_channel,
+                    int* frames) {
+    if (!st) return set_last_error("null stream");
+    if (channels) *channels = st->idx.ix.channels;
+    if (sample_rate) *sample_rate = st->idx.ix.rate;
+    if (samples_per_channel) *samples_per_channel = st->idx.ix.samples;
+    if (frames) *frames = int(st->idx.ix.frames.size());
+    return 0;
+}
+
+const gsc_index* gsc_stream_index(const gsc_stream* st) {
+    if (!st) {
+        set_last_error("null stream");
+        return nullptr;
+    }
+    return &st->idx;
+}
+
+int gsc_stream_device(const gsc_stream* st) { return st ? st->device : set_last_error("null stream"); }
+
+int gsc_decode_crops_variant(int variant) {
+    const int prev = t_crop_variant;
+    if (variant >= 0 && variant <= 2) t_crop_variant = variant;
+    return prev;
+}
+
+int gsc_decode_crops(gsc_stream* const* streams, int nstreams, const gsc_crop* crops, int ncrops, int dtype,
+                     int layout, long long length, void* dst_device, void* hip_stream, long long* written) {
+    const double t_begin = now_ms();
+    t_dtim = gsc_decode_timing{};
+    if (!streams || nstreams <= 0) return set_last_error("gsc_decode_crops: no streams");
+    if (dtype != GSC_PCM_INT16 && dtype != GSC_PCM_FLOAT32) return set_last_error("gsc_decode_crops: unknown dtype");
+    if (layout != GSC_LAYOUT_TC && layout != GSC_LAYOUT_CT) return set_last_error("gsc_decode_crops: unknown layout");
+    if (!dst_device) return set_last_error("gsc_decode_crops: dst_device is null");
+    std::vector<const Index*> ixs(static_cast<size_t>(nstreams), nullptr);
+    for (int s = 0; s < nstreams; ++s) {
+        if (!streams[s]) return set_last_error("gsc_decode_crops: stream " + std::to_string(s) + " is null");
+        ixs[size_t(s)] = &streams[s]->idx.ix;
+    }
+    std::vector<Crop> cr(static_cast<size_t>(std::max(ncrops, 0)));
+    if (ncrops > 0 && !crops) return set_last_error("gsc_decode_crops: crops is null");
+    for (int i = 0; i < ncrops; ++i) cr[size_t(i)] = Crop{crops[i].stream, crops[i].begin, crops[i].count};
+    CropPlan plan;
+    std::string err;
+    if (plan_crops(ixs.data(), nstreams, cr.data(), ncrops, length, &plan, &err) != 0) return set_last_error(err);
+    if (require_device() != 0) return -1;
+    int dev = 0;
+    DEC_TRY(hipGetDevice(&dev));
+    for (int s = 0; s < nstreams; ++s)
+        if (streams[s]->device != dev)
+            return set_last_error("gsc_decode_crops: stream " + std::to_string(s) + " lives on device " +
+                                  std::to_string(streams[s]->device) + ", the calling thread is bound to device " +
+                                  std::to_string(dev));
+    auto report = [&] {  // only once everything is enqueued: a failed call reports no output
+        for (int i = 0; i < ncrops; ++i)
+            if (written) written[i] = plan.crops[size_t(i)].count;
+        return 0;
+    };
+    if (ncrops == 0 || length == 0) return report();
+    const int C = plan.channels;
+    if (C <= 0 || length > (int64_t(1) << 40) / (int64_t(ncrops) * C))
+        return set_last_error("gsc_decode_crops: output too large for one call");
+    hipStream_t hs = static_cast<hipStream_t>(hip_stream);
+    // the call's own block: job descriptors, then the symbol scratch; stream-ordered, so calls on other
+    // streams never share it
+    const size_t njob = size_t(ncrops), npc = plan.pieces.size();
+    const size_t desc_bytes = (njob * sizeof(CropJob) + npc * sizeof(CropPiece) + 15) & ~size_t(15);
+    const bool fused = t_crop_variant == 2;  // no symbol scratch
+    const size_t sym_bytes = fused ? 0 : size_t(plan.slots) * kDecodeS * sizeof(uint16_t);
+    std::vector<unsigned char> host(desc_bytes, 0);
+    CropJob* hj = reinterpret_cast<CropJob*>(host.data());
+    int lds_bytes = 0;
+    for (size_t i = 0; i < njob; ++i) {
+        const PlanCrop& pc = plan.crops[i];
+        const gsc_stream& st = *streams[pc.stream];
+        const Slabs<ResFrame>& sl = st.slabs;
+        hj[i] = CropJob{sl.frames.p, sl.cps.p, sl.words(), sl.cb.p,  sl.att.p, sl.ncp, sl.nwords, sl.ncb,
+                        sl.natt,     pc.begin, pc.count,   int32_t(st.idx.ix.frames.size()),
+                        pc.f0,       pc.f1,    pc.piece0};
+        lds_bytes = std::max(lds_bytes, st.lds_bytes);
+    }
+    if (npc) std::memcpy(host.data() + njob * sizeof(CropJob), plan.pieces.data(), npc * sizeof(CropPiece));
+    unsigned char* d_block = nullptr;
+    DEC_TRY(hipMallocAsync(reinterpret_cast<void**>(&d_block), desc_bytes + std::max<size_t>(sym_bytes, 16), hs));
+    struct FreeAsync {
+        unsigned char* p;
+        hipStream_t s;
+        ~FreeAsync() { (void)hipFreeAsync(p, s); }
+    } guard{d_block, hs};
+    // pageable source: the runtime has taken the bytes when the call returns (it stages a small copy;
+    // one it cannot stage it completes first, and then this call waits for the stream's earlier work)
+    DEC_TRY(hipMemcpyAsync(d_block, host.data(), desc_bytes, hipMemcpyHostToDevice, hs));
+    const CropJob* d_jobs = reinterpret_cast<const CropJob*>(d_block);
+    const CropPiece* d_pieces = reinterpret_cast<const CropPiece*>(d_block + njob * sizeof(CropJob));
+    uint16_t* d_sym = reinterpret_cast<uint16_t*>(d_block + desc_bytes);
+    const int is_float = dtype == GSC_PCM_FLOAT32, planar = layout == GSC_LAYOUT_CT;
+    if (fused) {
+        // a workgroup per 4 Ki samples of a crop: 8 or 9 segments of a stereo ChunkSize-8 stream
+        DEC_TRY(gsc_launch_crop_fused(d_jobs, ncrops, length, C, is_float, planar, int(std::min<int64_t>(length, 4096)),
+                                      dst_device, hs));
+    } else {
+        DEC_TRY(gsc_launch_crop_unpack(d_jobs, ncrops, d_pieces, int(npc), d_sym, plan.slots, hs));
+        // LDS variant: a workgroup per 16 Ki samples of a crop
+        DEC_TRY(gsc_launch_crop_synth(d_jobs, ncrops, d_pieces, int(npc), d_sym, plan.slots, length, C, is_float,
+                                      planar, t_crop_variant == 1 ? lds_bytes : -1,
+                                      int(std::min<int64_t>(length, 16384)), dst_device, hs));
+    }
+    t_dtim.h2d_bytes = (long long)desc_bytes;
+    t_dtim.frames = int(npc);
+    t_dtim.symbols = plan.slots * kDecodeS;
+    t_dtim.samples = int64_t(ncrops) * length * C;
+    t_dtim.total_ms = now_ms() - t_begin;
+    return report();
+}
+
+int gsc_stream_decode_samples(gsc_stream* st, long long begin, long long count, int16_t* pcm) {
+    if (!st || (!pcm && count > 0)) return set_last_error("gsc_stream_decode_samples: invalid argument");
+    if (begin < 0 || count < 0 || begin > st->idx.ix.samples || count > st->idx.ix.samples - begin)
+        return set_last_error("gsc_stream_decode_samples: [" + std::to_string(begin) + ", " +
+                              std::to_string(begin) + " + " + std::to_string(count) + ") outside the stream's " +
+                              std::to_string(st->idx.ix.samples) + " samples");
+    if (count == 0) return 0;
+    if (require_device() != 0) return -1;
+    const size_t n = size_t(count) * size_t(st->idx.ix.channels);
+    Dev<int16_t> d_out;
+    DEC_TRY(d_out.alloc(n));
+    gsc_crop c{0, begin, count};
+    gsc_stream* one[1] = {st};
+    if (gsc_decode_crops(one, 1, &c, 1, GSC_PCM_INT16, GSC_LAYOUT_TC, count, d_out.p, nullptr, nullptr) != 0)
+        return -1;
+    const double t0 = now_ms();
+    DEC_TRY(hipMemcpy(pcm, d_out.p, n * sizeof(int16_t), hipMemcpyDeviceToHost));  // after the default stream's work
+    t_dtim.d2h_ms = now_ms() - t0;
+    t_dtim.total_ms += t_dtim.d2h_ms;
+    return 0;
+}
+
+}  // extern "C"

@@ -1,9 +1,13 @@
-// Device code the decode kernels share (gsc_decode.hip, gsc_decode_crops.hip):
-// the bit walk of one checkpoint segment and the sample arithmetic, each in
-// one place (decoder/decoder.lpr:163-203).
+// What the decode kernels and their launchers share (gsc_decode.hip,
+// gsc_decode_crops.hip), each in one place: the bit walk of one checkpoint
+// segment and the sample arithmetic (decoder/decoder.lpr:163-203), the
+// binary search, a frame's tables staged in LDS or read from global memory,
+// and the dynamic-LDS limit.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include <atomic>
 
 #include "gsc_decode.h"
 
@@ -66,6 +70,101 @@ __device__ __forceinline__ void symbol_fields(uint32_t w, int count, int cs, int
 // product wraps in 32 bits, it is not clamped
 __device__ __forceinline__ int16_t synth_sample(int lut, int v) {
     return (int16_t)(uint16_t)(((uint32_t)(lut * v)) >> 15);
+}
+
+// The last i of [lo, hi] with key(i) <= x; lo when there is none.
+template <typename Key>
+__device__ __forceinline__ int last_le(int lo, int hi, int64_t x, Key key) {
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (key(mid) <= x) {
+            lo = mid;
+        } else {
+            hi = mid - 1;
+        }
+    }
+    return lo;
+}
+
+// The codebook and attenuation slabs a frame's cb_off and att_off index.
+struct TableSlabs {
+    const int16_t* cb;
+    int64_t ncb;
+    const uint8_t* att;
+    int64_t natt;
+};
+
+// A frame's tables in a workgroup's dynamic LDS (stage_tables); StagedTables{}: not staged.
+struct StagedTables {
+    const int16_t* cb = nullptr;
+    const uint8_t* att = nullptr;
+    bool on = false;
+};
+
+// Whether a frame's tables fit lds_bytes and lie inside their slabs, so that
+// they can be copied to LDS word by word.
+__device__ __forceinline__ bool tables_staged(const FrameTables& f, const TableSlabs& g, int lds_bytes) {
+    const int64_t cbn = (int64_t)f.count * f.cs;
+    return staged_size(f.count, f.cs).bytes <= lds_bytes && f.cb_off >= 0 && (f.cb_off & 1) == 0 &&
+           f.cb_off + cbn + 1 <= g.ncb && f.att_off >= 0 && f.att_off + f.count <= g.natt;
+}
+
+// Every lane of a workgroup: copies the frame's tables to smem when
+// tables_staged says so.  The caller puts a barrier after it, and one before
+// it when smem is still being read.
+__device__ __forceinline__ StagedTables stage_tables(const FrameTables& f, const TableSlabs& g, int lds_bytes,
+                                                     unsigned char* smem, int tid, int threads) {
+    const int64_t att_at = staged_size(f.count, f.cs).att_at;
+    const StagedTables lds{reinterpret_cast<const int16_t*>(smem), smem + att_at, tables_staged(f, g, lds_bytes)};
+    if (lds.on) {
+        const uint32_t* src = reinterpret_cast<const uint32_t*>(g.cb + f.cb_off);
+        uint32_t* dst = reinterpret_cast<uint32_t*>(smem);
+        const int nw = (int)(((int64_t)f.count * f.cs + 1) / 2);
+        for (int i = tid; i < nw; i += threads) dst[i] = src[i];
+        for (int i = tid; i < f.count; i += threads) smem[att_at + i] = g.att[f.att_off + i];
+    }
+    return lds;
+}
+
+// Sample j of the chunk of symbol word w: from the staged tables, or from the
+// global slabs with every index clamped to its slab.
+__device__ __forceinline__ int16_t table_sample(const FrameTables& f, const int* lut, uint32_t w, int j,
+                                                const StagedTables& lds, const TableSlabs& g) {
+    int idx, neg, jj;
+    symbol_fields(w, f.count, f.cs, j, &idx, &neg, &jj);
+    int a, v;
+    if (lds.on) {
+        a = lds.att[idx];
+        v = lds.cb[idx * f.cs + jj];
+    } else {
+        int64_t ai = f.att_off + idx, ci = f.cb_off + (int64_t)idx * f.cs + jj;
+        ai = ai < 0 ? 0 : (ai >= g.natt ? g.natt - 1 : ai);
+        ci = ci < 0 ? 0 : (ci >= g.ncb ? g.ncb - 1 : ci);
+        a = g.att[ai];
+        v = g.cb[ci];
+    }
+    return synth_sample(lut[neg * 16 + (a & 15)], v);
+}
+
+// Raises the dynamic LDS a kernel may use once per device and size, not per
+// launch: the limit belongs to the kernel as loaded on one device, so what was
+// granted is remembered per device ordinal (past kDevices, asked every time).
+struct LdsLimit {
+    static constexpr int kDevices = 16;
+    std::atomic<int> granted[kDevices] = {};
+};
+template <typename K>
+hipError_t allow_lds(K kernel, int lds_bytes, LdsLimit* lim) {
+    if (lds_bytes <= 32 * 1024) return hipSuccess;
+    int dev = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e != hipSuccess) return e;
+    std::atomic<int>* slot = dev >= 0 && dev < LdsLimit::kDevices ? &lim->granted[dev] : nullptr;
+    if (slot && lds_bytes <= slot->load(std::memory_order_relaxed)) return hipSuccess;
+    e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                            lds_bytes);
+    if (e == hipSuccess && slot) slot->store(lds_bytes, std::memory_order_relaxed);
+    return e;
 }
 
 }  // namespace gsc

@@ -1398,7 +1398,7 @@ int Encoder::encode_range(int b, int e, std::vector<uint8_t>* out, std::string* 
     return 0;
 }
 
-// the calling thread's error slot and the device check, for gsc_decode.cpp
+// the calling thread's error slot and the device check, for gsc_decode_abi.cpp
 int set_last_error(const std::string& m) { return fail(m); }
 int require_device() { return ensure_device(); }
 

@@ -1,4 +1,4 @@
-"""The decoder's host index (gsc_decode.cpp's sequential walk) without a GPU.
+"""The decoder's host index (gsc_decode_index.cpp's sequential walk) without a GPU.
 
 Frame offsets are pinned by the oracle alone: the bytes between two offsets,
 decoded by the oracle as a stream of their own, must give the oracle's

@@ -231,6 +231,31 @@ def test_other_variants_large_codebooks(sc, pair, other_variant):
     _check(sc, list(pair), BATCH, 3600)
 
 
+def test_lds_limit_on_two_devices(sc):
+    """The LDS variant needs its dynamic-LDS limit raised above 32 KiB on
+    every device it runs on: the 4096 x 16, 12-bit frame (132 KiB of tables)
+    resident on device 0, then on device 1, in one process."""
+    import torch
+
+    if torch.cuda.device_count() < 2:
+        pytest.skip("needs two devices")
+    rng = np.random.default_rng(46)
+    gsc = gw.random_frame(rng, 2 * 600, ch=2, count=4096, cs=16, bd=12, policy="once")
+    device, variant = torch.cuda.current_device(), sc.Decoder.crop_variant("lds")
+    try:
+        for d in (0, 1):
+            torch.cuda.set_device(d)
+            sc.set_device(d)
+            r = Res(sc, gsc)
+            assert r.st.device == d
+            _check(sc, [r], [(0, 0, 9600), (0, 9590, 10)], 9600)
+            r.st.close()
+    finally:
+        torch.cuda.set_device(device)
+        sc.set_device(device)
+        sc.Decoder.crop_variant(variant)
+
+
 def test_other_variants_at_the_edges(sc, other_variant):
     """The chunk, checkpoint and frame edges again under the other variants:
     frames of different ChunkSize, ChunkCount and bit depth (the 12-bit one with

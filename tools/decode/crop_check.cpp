@@ -1,5 +1,5 @@
 // Stand-alone driver of the decoder's sample locator and crop planner
-// (gsc_decode.cpp built with GSC_DECODE_WALK_ONLY: gsc::index_locate, which
+// (gsc_decode_index.cpp, which needs no HIP: gsc::index_locate, which
 // gsc_index_locate wraps, and gsc::plan_crops, which gsc_decode_crops runs
 // before it launches anything), meant for a host sanitizer build:
 //   make -C soundchunks_amd/csrc crop_check

@@ -1,5 +1,5 @@
-// Stand-alone driver of the decoder's host walk (gsc_decode.cpp built with
-// GSC_DECODE_WALK_ONLY), meant for a host sanitizer build:
+// Stand-alone driver of the decoder's host walk (gsc_decode_index.cpp, which
+// needs no HIP), meant for a host sanitizer build:
 //   make -C soundchunks_amd/csrc walk_check
 //   soundchunks_amd/lib/decode_walk_check FILE.gsc...
 // Every file is copied into a heap block of exactly its size, so a read past
