@@ -301,6 +301,60 @@ int gsc_stream_decode_samples(gsc_stream *st, long long begin, long long count, 
  * value; any other argument only queries.  The output does not depend on it. */
 int gsc_decode_crops_variant(int variant);
 
+/* ---- seek tables: opening a stream without the host walk -------------------- */
+/* A seek table is a side blob that holds what the walk finds by following the
+ * stream's two chains: where every frame starts, how many bits its bitstream
+ * has, and every checkpoint.  The .gsc bytes are not touched.  Little-endian,
+ * version 1, exactly 32 + 16 F + 8 P bytes:
+ *
+ *   offset      field
+ *   0           magic "GSCT"
+ *   4           u32 version = 1
+ *   8           u32 S, gsc_decode_checkpoint_symbols() of the writer
+ *   12          u32 F, frame count
+ *   16          u64 stream length in bytes
+ *   24          u64 P, checkpoints of all frames
+ *   32          F x { u64 byte offset of the frame, u64 bits of its bitstream }
+ *   32 + 16 F   P x u64 checkpoint, frames in order: bit offset within the
+ *               frame's bitstream << 3 | (variableCodingHeader on entry + 1);
+ *               a frame has ceil(FrameLength * ChannelCount / S) of them
+ *
+ * A table is never trusted.  The host checks what needs no symbol walk (the
+ * sizes, S, the stream length, every frame header at its claimed offset with
+ * the validations of gsc_index_create, the checkpoint counts and ranges, and
+ * that the claimed bit counts chain the frames exactly to the stream's end);
+ * then one device lane per checkpoint walks its segment and must land exactly
+ * on the next checkpoint, or on the frame's bit count, without meeting a chunk
+ * index >= ChunkCount.  A frame's first checkpoint is (0, -1) by definition,
+ * so a table that passes is the one the walk would have written: opening with
+ * a table succeeds if and only if gsc_index_create accepts the stream and
+ * gsc_index_table of that index equals the table byte for byte, and the index
+ * is then the same.  Otherwise NULL and gsc_last_error, which names the frame
+ * and the checkpoint; nothing stays allocated.  A table written with another S
+ * is refused. */
+/* the table of any index: *table (release with gsc_free), *len bytes.  Host only. */
+int gsc_index_table(const gsc_index *ix, uint8_t **table, size_t *len);
+/* gsc_index_create without the walk.  Needs the device: the stream's bytes and
+ * the checkpoints are uploaded for the check and freed again.
+ * gsc_index_create remains the way that needs none. */
+gsc_index *gsc_index_create_with_table(const uint8_t *gsc, size_t len, const uint8_t *table, size_t table_len);
+/* gsc_stream_open without the walk: one upload, checked against the resident slabs */
+gsc_stream *gsc_stream_open_with_table(const uint8_t *gsc, size_t len, const uint8_t *table, size_t table_len);
+/* gsc_encode_prepared that also returns the table of the bytes it returns
+ * (offsets relative to them: a frame range is a stream of its own), straight
+ * from the index packer, which knows every checkpoint.  One file only. */
+int gsc_encode_prepared_with_table(gsc_prepared *p, int frame_begin, int frame_end, uint8_t **out, size_t *out_len,
+                                   uint8_t **table, size_t *table_len);
+/* Timing of the last gsc_stream_open, gsc_stream_open_with_table or
+ * gsc_index_create_with_table on the calling thread (milliseconds): host_ms is
+ * the walk, or with a table the frame headers and the codebook / attenuation
+ * tables; verify_ms the check on the device (0 without a table). */
+typedef struct {
+    double host_ms, upload_ms, verify_ms, total_ms;
+    long long uploaded_bytes, checkpoints;
+} gsc_open_timing;
+void gsc_last_open_timing(gsc_open_timing *t);
+
 /* Timing of the last gsc_decode*, gsc_stream_open or crop call on the calling
  * thread (milliseconds).  h2d_bytes: the bytes that call uploaded. */
 typedef struct {

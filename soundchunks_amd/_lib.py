@@ -78,6 +78,19 @@ class GscDecodeTiming(ctypes.Structure):
     ]
 
 
+class GscOpenTiming(ctypes.Structure):
+    """Mirror of ``gsc_open_timing``."""
+
+    _fields_ = [
+        ("host_ms", ctypes.c_double),
+        ("upload_ms", ctypes.c_double),
+        ("verify_ms", ctypes.c_double),
+        ("total_ms", ctypes.c_double),
+        ("uploaded_bytes", ctypes.c_longlong),
+        ("checkpoints", ctypes.c_longlong),
+    ]
+
+
 class GscCrop(ctypes.Structure):
     """Mirror of ``gsc_crop``: per-channel sample positions of one stream."""
 
@@ -138,6 +151,9 @@ SIGNATURES = {
                                            ctypes.POINTER(ctypes.c_size_t)]),
     "gsc_encode_prepared_frames": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(_U8P),
                                                   ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_size_t)]),
+    "gsc_encode_prepared_with_table": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
+                                                      ctypes.POINTER(_U8P), ctypes.POINTER(ctypes.c_size_t),
+                                                      ctypes.POINTER(_U8P), ctypes.POINTER(ctypes.c_size_t)]),
     "gsc_prepared_prepare_ms": (ctypes.c_double, [ctypes.c_void_p]),
     "gsc_prepared_free": (None, [ctypes.c_void_p]),
     "gsc_frame_dsp": (ctypes.c_int, [_U8P, ctypes.c_size_t, ctypes.POINTER(GscOptions), ctypes.c_int, _IP,
@@ -153,6 +169,10 @@ SIGNATURES = {
     "gsc_index_info": (ctypes.c_int, [ctypes.c_void_p, _IP, _IP, _LLP]),
     "gsc_index_frames": (ctypes.c_int, [ctypes.c_void_p, _SZP, _IP, _IP, _IP, _LLP]),
     "gsc_index_free": (None, [ctypes.c_void_p]),
+    "gsc_index_table": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(_U8P), _SZP]),
+    "gsc_index_create_with_table": (ctypes.c_void_p, [_U8P, ctypes.c_size_t, _U8P, ctypes.c_size_t]),
+    "gsc_stream_open_with_table": (ctypes.c_void_p, [_U8P, ctypes.c_size_t, _U8P, ctypes.c_size_t]),
+    "gsc_last_open_timing": (None, [ctypes.POINTER(GscOpenTiming)]),
     "gsc_decode_checkpoint_symbols": (ctypes.c_int, []),
     "gsc_index_locate": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_longlong, _IP, _LLP, _IP, _LLP]),
     "gsc_stream_open": (ctypes.c_void_p, [_U8P, ctypes.c_size_t]),

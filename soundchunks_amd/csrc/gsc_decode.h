@@ -5,6 +5,7 @@
 #pragma once
 #include <cstddef>
 #include <cstdint>
+#include <functional>
 #include <string>
 #include <vector>
 
@@ -60,7 +61,7 @@ struct DecJob {
 
 // A checkpoint: bit offset within the frame's bitstream << 3 | (header + 1),
 // header = variableCodingHeader on entry (-1 .. 3, decoder.lpr:173-186).
-inline uint64_t make_checkpoint(uint64_t bit, int header) { return bit << 3 | uint64_t(header + 1); }
+constexpr uint64_t make_checkpoint(uint64_t bit, int header) { return bit << 3 | uint64_t(header + 1); }
 
 struct IndexFrame {
     size_t off = 0, att_off = 0, cb_off = 0, bs_off = 0, end_off = 0;  // byte offsets in the file
@@ -89,6 +90,44 @@ struct Index {
 // The sequential pass (host only): frame offsets, checkpoints, lookup tables,
 // and every validation.  0, or -1 with *err set; never reads outside [g, g + len).
 int decode_walk(const uint8_t* g, size_t len, Index* ix, std::string* err);
+
+// ---- seek tables ------------------------------------------------------------
+// What the walk finds by following the two chains, as a side blob (layout:
+// include/soundchunks.h): per frame its byte offset and the bits of its
+// bitstream, then every checkpoint.  Little-endian, 32 + 16 F + 8 P bytes.
+constexpr size_t kTableHeaderBytes = 32;
+constexpr uint32_t kTableVersion = 1;
+void index_table_write(const Index& ix, std::vector<uint8_t>* out);
+
+// runs fn(0 .. n - 1), possibly on several threads; frames are independent
+using ParallelRunner = std::function<void(int n, const std::function<void(int)>& fn)>;
+
+// The host half of opening a stream with a table: the index the walk would
+// have built if every claim of the table holds.  It checks what needs no
+// symbol walk (sizes, magic, version, S, the stream's length, every frame
+// header at its claimed offset, checkpoint counts and ranges, and that the
+// claimed bitstream lengths chain the frames exactly to `len`) and fills
+// frames, cps, codebook, att and the totals as decode_walk does, O(frames)
+// plus the tables (built through `par` when given).  Whether the checkpoints
+// and bit counts are the stream's own is left to decode_verify_kernel
+// (gsc_decode.hip); an index from here must not be used before that passed.
+// 0, or -1 with *err set; never reads outside [g, g + len) or the table.
+int index_from_table(const uint8_t* g, size_t len, const uint8_t* table, size_t tlen, Index* ix, std::string* err,
+                     const ParallelRunner* par = nullptr);
+
+// ---- decode_verify_kernel's report -----------------------------------------
+// One status word: kVerifyOk, or the smallest failing checkpoint (counted over
+// the whole stream) << 8 | reason, so that the report does not depend on
+// which lane came first.
+constexpr unsigned long long kVerifyOk = ~0ull;
+enum VerifyReason : int {
+    kVerifyBounds = 1,  // a descriptor points outside its slab
+    kVerifyIndex = 2,   // a chunk index >= ChunkCount
+    kVerifyBit = 3,     // the segment ends at another bit offset than claimed
+    kVerifyHeader = 4,  // ... in another header state than claimed
+};
+// the text of a status word other than kVerifyOk
+std::string verify_message(const Index& ix, unsigned long long status);
 
 // ---- sample ranges of resident streams (gsc_decode_crops.hip) -------------------
 // A per-channel sample position in [0, samples): the frame that contains it

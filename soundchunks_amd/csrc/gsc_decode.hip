@@ -6,6 +6,9 @@
 //                         and writes one u16 word per symbol,
 //                         idx << 2 | neg << 1 | rev (pack_kernel's codes_out
 //                         and recon_kernel's chunk word)
+//   decode_verify_kernel  the same lanes and the same walk (walk_segment,
+//                         gsc_decode_device.h) over a claimed seek table:
+//                         nothing is written but one status word
 //   decode_synth_kernel   one lane per output sample: the low 16 bits of
 //                         (CAttrLookup[neg][att[idx]] * chunk[idx][j']) >> 15
 //                         in 32-bit arithmetic (the reference wraps, it does
@@ -42,6 +45,48 @@ __global__ __launch_bounds__(kUnpackThreads) void decode_unpack_kernel(const Dec
     const int64_t so = f.sym_off + s0;
     if (so < 0 || so + n > nsym || f.bs_off < 0) return;
     unpack_segment(words, nwords, f.bs_off, cps[c], f.ver, f.count, n, sym + so);
+}
+
+// A claimed seek table against the stream (gsc_decode_index.cpp,
+// index_from_table): one lane per checkpoint segment, the frame found as
+// above.  The lane walks its segment from checkpoint c and must land on
+// checkpoint c + 1 in bit offset and header state, or, in the frame's last
+// segment, on the frame's claimed bit count (the header state is free there);
+// no raw index may reach ChunkCount.  A frame's checkpoint 0 is (0, -1) by
+// definition (the host checked it), so when no lane objects every checkpoint
+// is the one the sequential walk would have left.  A lane that objects
+// lowers *status to its checkpoint << 8 | reason: the smallest one wins,
+// whichever lane comes first.
+__global__ __launch_bounds__(kUnpackThreads) void decode_verify_kernel(const ResFrame* __restrict__ frames,
+                                                                       const uint64_t* __restrict__ frame_bits,
+                                                                       int nframes, const uint64_t* __restrict__ cps,
+                                                                       int64_t ncp, const uint32_t* __restrict__ words,
+                                                                       int64_t nwords,
+                                                                       unsigned long long* __restrict__ status) {
+    const int64_t c = (int64_t)blockIdx.x * kUnpackThreads + threadIdx.x;
+    if (c >= ncp) return;
+    const int fi = last_le(0, nframes - 1, c, [&](int i) { return frames[i].cp_first; });
+    const ResFrame& f = frames[fi];
+    const int64_t s0 = (c - f.cp_first) * kDecodeS;
+    int reason = 0;
+    if (s0 < 0 || s0 >= f.nsym || f.bs_off < 0) {
+        reason = kVerifyBounds;
+    } else {
+        const int n = (int)(f.nsym - s0 < kDecodeS ? f.nsym - s0 : kDecodeS);
+        const bool last = s0 + n == f.nsym;
+        if (!last && c + 1 >= ncp) {
+            reason = kVerifyBounds;
+        } else {
+            const int count = f.count;
+            bool over = false;
+            const WalkEnd end = walk_segment(words, nwords, f.bs_off, cps[c], f.ver, n,
+                                             [&](int, int idx, uint32_t, uint32_t) { over |= idx >= count; });
+            const uint64_t want = last ? make_checkpoint(frame_bits[fi], end.hdr) : cps[c + 1];
+            const uint64_t got = make_checkpoint(end.bit, end.hdr);
+            reason = over ? kVerifyIndex : (got >> 3) != (want >> 3) ? kVerifyBit : got != want ? kVerifyHeader : 0;
+        }
+    }
+    if (reason) atomicMin(status, (unsigned long long)c << 8 | (unsigned long long)reason);
 }
 
 __global__ __launch_bounds__(kDecodeSynthThreads) void decode_synth_kernel(
@@ -89,6 +134,17 @@ extern "C" hipError_t gsc_launch_decode_unpack(const DecFrame* frames, int nfram
     const unsigned grid = (unsigned)((ncp + kUnpackThreads - 1) / kUnpackThreads);
     hipLaunchKernelGGL(decode_unpack_kernel, dim3(grid), dim3(kUnpackThreads), 0, st, frames, nframes, cps, ncp, words,
                        nwords, sym, nsym);
+    return hipGetLastError();
+}
+
+// *status must hold kVerifyOk; frame_bits: the claimed bit count of every frame
+extern "C" hipError_t gsc_launch_decode_verify(const ResFrame* frames, const uint64_t* frame_bits, int nframes,
+                                               const uint64_t* cps, int64_t ncp, const uint32_t* words, int64_t nwords,
+                                               unsigned long long* status, hipStream_t st) {
+    if (nframes <= 0 || ncp <= 0) return hipSuccess;
+    const unsigned grid = (unsigned)((ncp + kUnpackThreads - 1) / kUnpackThreads);
+    hipLaunchKernelGGL(decode_verify_kernel, dim3(grid), dim3(kUnpackThreads), 0, st, frames, frame_bits, nframes, cps,
+                       ncp, words, nwords, status);
     return hipGetLastError();
 }
 

@@ -1,8 +1,9 @@
 // .gsc decoder, HIP runtime side and C ABI.
 //
-// decode_parts uploads the frames a call asks for, as gsc_decode_index.cpp's
-// walk indexed them, and runs gsc_decode.hip's two stages over all of them.  A
-// resident stream (gsc_stream_open) keeps the index and the bytes on the
+// decode_parts uploads the frames a call asks for, as gsc_decode_index.cpp
+// indexed them (the walk, or a seek table checked on the device), and runs
+// gsc_decode.hip's two stages over all of them.  A resident stream
+// (gsc_stream_open, gsc_stream_open_with_table) keeps the index and the bytes on the
 // device; gsc_decode_crops then decodes batches of sample ranges into
 // caller-owned device memory (plan_crops; gsc_decode_crops.hip).  Both keep
 // their device copies in a Slabs and describe a frame with frame_tables.
@@ -26,6 +27,10 @@ extern "C" hipError_t gsc_launch_decode_synth(const gsc::DecFrame* frames, int n
                                               const int16_t* cb, int64_t ncb, const uint8_t* att, int64_t natt,
                                               int16_t* out, int64_t nout, hipStream_t st);
 
+extern "C" hipError_t gsc_launch_decode_verify(const gsc::ResFrame* frames, const uint64_t* frame_bits, int nframes,
+                                               const uint64_t* cps, int64_t ncp, const uint32_t* words, int64_t nwords,
+                                               unsigned long long* status, hipStream_t st);
+
 extern "C" hipError_t gsc_launch_crop_unpack(const gsc::CropJob* jobs, int ncrops, const gsc::CropPiece* pieces,
                                              int npieces, uint16_t* sym, int64_t nslots, hipStream_t st);
 extern "C" hipError_t gsc_launch_crop_synth(const gsc::CropJob* jobs, int ncrops, const gsc::CropPiece* pieces,
@@ -43,10 +48,14 @@ namespace gsc {
 
 int set_last_error(const std::string& m);
 int require_device();
+// the host worker pool (gsc_runtime.cpp)
+void parallel_for(int n, int threads, const std::function<void(int)>& fn);
+int host_threads();
 
 namespace {
 
 thread_local gsc_decode_timing t_dtim;
+thread_local gsc_open_timing t_otim;  // the last gsc_stream_open* / gsc_index_create_with_table
 // crop decode: 0 unpack, then synthesis with the codebook from global memory; 1 the same with the codebook
 // staged in LDS; 2 unpack and synthesis fused in one launch (DESIGN.md "f5 decoder" has the A/B)
 thread_local int t_crop_variant = 2;
@@ -424,38 +433,136 @@ void gsc_stream_free(gsc_stream* st) {
     if (sw) (void)hipSetDevice(cur);
 }
 
-static int stream_open(const uint8_t* gsc, size_t len, gsc_stream* h) {
-    const double t0 = now_ms();
-    std::string err;
-    if (decode_walk(gsc, len, &h->idx.ix, &err) != 0) return set_last_error(err);
-    const Index& ix = h->idx.ix;
-    t_dtim.host_index_ms = now_ms() - t0;
-    if (require_device() != 0) return -1;
-    DEC_TRY(hipGetDevice(&h->device));
+// A stream's index to the device, at position 0 of `s`: the bytes and the
+// checkpoints, with_tables also the codebooks and attenuations; the frame table.
+static int upload_resident(const uint8_t* gsc, const Index& ix, bool with_tables, Slabs<ResFrame>* s,
+                           int* lds_bytes) {
     std::vector<ResFrame> frames(ix.frames.size());
     for (size_t i = 0; i < frames.size(); ++i) {
         const IndexFrame& f = ix.frames[i];
         static_cast<FrameTables&>(frames[i]) = frame_tables(f, SlabPos{});
         frames[i].first_sample = f.first_sample;
-        h->lds_bytes = std::max(h->lds_bytes, frame_lds_bytes(f));
+        if (lds_bytes) *lds_bytes = std::max(*lds_bytes, frame_lds_bytes(f));
     }
-    const double t1 = now_ms();
-    const Span all = span_of(ix, 0, int(frames.size()));  // the whole stream, at position 0
-    if (h->slabs.alloc(all.count, frames.size()) != 0 || h->slabs.put(all, SlabPos{}, gsc, ix) != 0 ||
-        h->slabs.put_frames(frames) != 0)
+    Span all = span_of(ix, 0, int(frames.size()));  // the whole stream
+    if (!with_tables) all.count.cb = all.count.att = 0;
+    if (s->alloc(all.count, frames.size()) != 0 || s->put(all, SlabPos{}, gsc, ix) != 0 || s->put_frames(frames) != 0)
         return -1;
     DEC_TRY(hipDeviceSynchronize());
-    t_dtim.h2d_ms = now_ms() - t1;
+    return 0;
+}
+
+// decode_verify_kernel over an uploaded stream whose index came from a table:
+// 0 when every claim holds, else -1 with the first failing checkpoint named.
+static int verify_resident(const Index& ix, const Slabs<ResFrame>& s) {
+    if (ix.cps.size() >= (size_t(1) << 31) || ix.frames.size() >= (size_t(1) << 31))
+        return set_last_error("gsc decode: stream too large for one call");
+    std::vector<uint64_t> bits(ix.frames.size());
+    for (size_t i = 0; i < bits.size(); ++i) bits[i] = ix.frames[i].nbits;
+    Dev<uint64_t> d_bits;
+    Dev<unsigned long long> d_status;
+    unsigned long long status = kVerifyOk;
+    DEC_TRY(d_bits.alloc(bits.size()));
+    DEC_TRY(d_status.alloc(1));
+    DEC_TRY(hipMemcpy(d_bits.p, bits.data(), bits.size() * sizeof(uint64_t), hipMemcpyHostToDevice));
+    DEC_TRY(hipMemcpy(d_status.p, &status, sizeof(status), hipMemcpyHostToDevice));
+    DEC_TRY(gsc_launch_decode_verify(s.frames.p, d_bits.p, int(bits.size()), s.cps.p, s.ncp, s.words(), s.nwords,
+                                     d_status.p, nullptr));
+    DEC_TRY(hipMemcpy(&status, d_status.p, sizeof(status), hipMemcpyDeviceToHost));  // after the kernel
+    return status == kVerifyOk ? 0 : set_last_error(verify_message(ix, status));
+}
+
+// The index of a stream for an open: the walk, or with a table its host half
+// (the device half follows the upload).
+static int open_index(const uint8_t* gsc, size_t len, const uint8_t* table, size_t table_len, Index* ix) {
+    const double t0 = now_ms();
+    std::string err;
+    const ParallelRunner par = [](int n, const std::function<void(int)>& fn) { parallel_for(n, host_threads(), fn); };
+    const int rc = table ? index_from_table(gsc, len, table, table_len, ix, &err, &par) : decode_walk(gsc, len, ix, &err);
+    if (rc != 0) return set_last_error(err);
+    t_otim.host_ms = now_ms() - t0;
+    t_otim.checkpoints = (long long)ix->cps.size();
+    return 0;
+}
+
+// upload, and with a table the check on the device; the timing of both
+static int open_device(const uint8_t* gsc, const Index& ix, bool with_table, bool with_tables, Slabs<ResFrame>* s,
+                       int* lds_bytes) {
+    if (require_device() != 0) return -1;
+    const double t1 = now_ms();
+    if (upload_resident(gsc, ix, with_tables, s, lds_bytes) != 0) return -1;
+    const double t2 = now_ms();
+    t_otim.upload_ms = t2 - t1;
+    t_otim.uploaded_bytes = s->h2d_bytes;
+    if (with_table) {
+        if (verify_resident(ix, *s) != 0) return -1;
+        t_otim.verify_ms = now_ms() - t2;
+    }
+    return 0;
+}
+
+static int stream_open(const uint8_t* gsc, size_t len, const uint8_t* table, size_t table_len, gsc_stream* h) {
+    const double t0 = now_ms();
+    if (open_index(gsc, len, table, table_len, &h->idx.ix) != 0) return -1;
+    const Index& ix = h->idx.ix;
+    t_dtim.host_index_ms = t_otim.host_ms;
+    if (require_device() != 0) return -1;
+    DEC_TRY(hipGetDevice(&h->device));
+    if (open_device(gsc, ix, table != nullptr, true, &h->slabs, &h->lds_bytes) != 0) return -1;
+    t_dtim.h2d_ms = t_otim.upload_ms;
     t_dtim.h2d_bytes = h->slabs.h2d_bytes;
-    t_dtim.frames = int(frames.size());
-    t_dtim.total_ms = now_ms() - t0;
+    t_dtim.frames = int(ix.frames.size());
+    t_dtim.total_ms = t_otim.total_ms = now_ms() - t0;
     return 0;
 }
 
 gsc_stream* gsc_stream_open(const uint8_t* gsc, size_t len) {
     t_dtim = gsc_decode_timing{};
+    t_otim = gsc_open_timing{};
     std::unique_ptr<gsc_stream> h(new gsc_stream());
-    return stream_open(gsc, len, h.get()) == 0 ? h.release() : nullptr;
+    return stream_open(gsc, len, nullptr, 0, h.get()) == 0 ? h.release() : nullptr;
+}
+
+gsc_stream* gsc_stream_open_with_table(const uint8_t* gsc, size_t len, const uint8_t* table, size_t table_len) {
+    t_dtim = gsc_decode_timing{};
+    t_otim = gsc_open_timing{};
+    if (!table) {
+        set_last_error("gsc_stream_open_with_table: table is null");
+        return nullptr;
+    }
+    // a refused table frees the stream, and with it every slab it uploaded
+    std::unique_ptr<gsc_stream> h(new gsc_stream());
+    return stream_open(gsc, len, table, table_len, h.get()) == 0 ? h.release() : nullptr;
+}
+
+gsc_index* gsc_index_create_with_table(const uint8_t* gsc, size_t len, const uint8_t* table, size_t table_len) {
+    t_otim = gsc_open_timing{};
+    if (!table) {
+        set_last_error("gsc_index_create_with_table: table is null");
+        return nullptr;
+    }
+    const double t0 = now_ms();
+    std::unique_ptr<gsc_index> h(new gsc_index());
+    Slabs<ResFrame> s;  // the bytes and the checkpoints, for the check alone
+    if (open_index(gsc, len, table, table_len, &h->ix) != 0 || open_device(gsc, h->ix, true, false, &s, nullptr) != 0)
+        return nullptr;
+    t_otim.total_ms = now_ms() - t0;
+    return h.release();
+}
+
+int gsc_index_table(const gsc_index* ix, uint8_t** table, size_t* len) {
+    if (!ix || !table || !len) return set_last_error("gsc_index_table: invalid argument");
+    std::vector<uint8_t> t;
+    index_table_write(ix->ix, &t);
+    *table = static_cast<uint8_t*>(std::malloc(std::max<size_t>(t.size(), 1)));
+    if (!*table) return set_last_error("gsc_index_table: out of memory");
+    std::memcpy(*table, t.data(), t.size());
+    *len = t.size();
+    return 0;
+}
+
+void gsc_last_open_timing(gsc_open_timing* t) {
+    if (t) *t = t_otim;
 }
 
 int gsc_stream_info(const gsc_stream* st, int* channels, int* sample_rate, long long* samples_per_channel,

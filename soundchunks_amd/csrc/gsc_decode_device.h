@@ -13,22 +13,30 @@
 
 namespace gsc {
 
-// Walks n symbols (n <= kDecodeS) from checkpoint cp of a bitstream that
-// starts at byte bs_off of the word slab, and writes one word per symbol,
-// idx << 2 | neg << 1 | rev, to o[0 .. n).  The bytes are read as aligned
-// 32-bit words; a word past nwords reads as zero, an index past count - 1 is
-// clamped.  The caller checked bs_off >= 0 and that o holds n words.
-__device__ __forceinline__ void unpack_segment(const uint32_t* __restrict__ words, int64_t nwords, int64_t bs_off,
-                                               uint64_t cp, int ver, int count, int n, uint16_t* o) {
+// Where a segment's walk ended: the bit offset within the frame's bitstream
+// and variableCodingHeader, in make_checkpoint's form.
+struct WalkEnd {
+    uint64_t bit;
+    int hdr;
+};
+
+// The bit walk, in one place: n symbols (n <= kDecodeS) from checkpoint cp of
+// a bitstream that starts at byte bs_off of the word slab; sink(i, idx, neg,
+// rev) takes symbol i with its raw index (nothing clamped).  The bytes are
+// read as aligned 32-bit words; a word past nwords reads as zero.  The caller
+// checked bs_off >= 0.
+template <typename Sink>
+__device__ __forceinline__ WalkEnd walk_segment(const uint32_t* __restrict__ words, int64_t nwords, int64_t bs_off,
+                                                uint64_t cp, int ver, int n, Sink sink) {
     int hdr = (int)(cp & 7) - 1;  // variableCodingHeader on entry
     hdr = hdr > 3 ? 3 : hdr;
     const uint64_t bit = (cp >> 3) + (uint64_t)bs_off * 8;
     int64_t w = (int64_t)(bit >> 5);
     const int sh = (int)(bit & 31);
     const int rev_bit = ver > 0 ? 1 : 0;
-    const int idx_max = count > 0 ? count - 1 : 0;
     uint64_t buf = (w >= 0 && w < nwords ? words[w] : 0u) >> sh;
     int have = 32 - sh;
+    int walked = 0;  // bits consumed: at most 17 * kDecodeS
     ++w;
     for (int i = 0; i < n; ++i) {
         if (have <= 32) {  // refill: 33 bits or more, a symbol has at most 17
@@ -52,9 +60,22 @@ __device__ __forceinline__ void unpack_segment(const uint32_t* __restrict__ word
         used += 3 * (hdr + 1);
         buf >>= used;
         have -= used;
+        walked += used;
+        sink(i, idx, neg, rev);
+    }
+    return WalkEnd{(cp >> 3) + (uint64_t)walked, hdr};
+}
+
+// The walk with one word per symbol, idx << 2 | neg << 1 | rev, written to
+// o[0 .. n); an index past count - 1 is clamped.  The caller checked that o
+// holds n words.
+__device__ __forceinline__ void unpack_segment(const uint32_t* __restrict__ words, int64_t nwords, int64_t bs_off,
+                                               uint64_t cp, int ver, int count, int n, uint16_t* o) {
+    const int idx_max = count > 0 ? count - 1 : 0;
+    (void)walk_segment(words, nwords, bs_off, cp, ver, n, [&](int i, int idx, uint32_t neg, uint32_t rev) {
         idx = idx > idx_max ? idx_max : idx;
         o[i] = (uint16_t)((uint32_t)idx << 2 | neg << 1 | rev);
-    }
+    });
 }
 
 // The fields of a symbol word for sample j of its chunk: the chunk index

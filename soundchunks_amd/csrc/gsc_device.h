@@ -101,7 +101,7 @@ struct PackFrame {
     int64_t w_off;        // bitstream: pack_word_capacity(N) zeroed u32 words at words + w_off
     int32_t N, R;         // chunkRefs count, reducedChunks count before pruning (-pr0 passthrough: N)
     int32_t nbits;        // out: bits of the stream (16-bit words written = ceil(nbits / 16))
-    int32_t pad_;
+    int32_t cp_off;       // with a seek table: the frame's first checkpoint in the call's checkpoint slab
 };
 
 // u32 words that hold the index stream of n chunks (<= 17 bits per code)

@@ -65,6 +65,7 @@ struct FrameState {
     // KNNFit
     std::vector<int> best;     // N
     std::vector<uint8_t> stream;
+    int nbits = 0;             // bits of the index bitstream (pack_kernel)
 };
 
 // Builds the exact FPC trig tables for chunk size cs (not thread-safe: call
@@ -115,9 +116,12 @@ class Encoder {
         const int sc = fr_end_[size_t(i)] - fr_start_[size_t(i)] + 1;
         return ((sc - 1) / opt_.chunk_size + 1) * channels_;
     }
-    // Encode frames [b, e) and return their concatenated stream bytes
+    // Encode frames [b, e) and return their concatenated stream bytes; with
+    // `table`, also the decoder's seek table of those bytes (gsc_decode.h),
+    // its checkpoints emitted by the index packer
     int encode_range(int b, int e, std::vector<uint8_t>* out, std::string* err, gsc_timing* tim,
-                     ReconOut* recon = nullptr, std::vector<size_t>* frame_bytes = nullptr);
+                     ReconOut* recon = nullptr, std::vector<size_t>* frame_bytes = nullptr,
+                     std::vector<uint8_t>* table = nullptr);
     // Device DSP of frame f alone (parity tests): attenuation divider and the
     // N x 2CS features
     int dsp_frame(int f, int* atten_div, std::vector<float>* feat, std::string* err);

@@ -22,12 +22,16 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "gsc_decode.h"
 #include "gsc_device.h"
 
 namespace gsc {
 
 constexpr int kPackThreads = 1024;
 constexpr int kPackPerThread = 8;  // consecutive chunks per thread per tile
+// a thread's first chunk of a tile is a multiple of kPackPerThread, so a
+// decoder checkpoint (every kDecodeS symbols) is always some thread's element 0
+static_assert(kDecodeS % kPackPerThread == 0, "checkpoints must fall on element 0 of a packer thread");
 
 // vcbsCnt of a reduced-chunk index (encoder.lpr:1054): 0 for index 0, else
 // BsrWord(index) div CVariableCodingBlockSize
@@ -66,9 +70,15 @@ __global__ __launch_bounds__(1024) void usecount_kernel(const PackFrame* __restr
 // best bit 0 (encoder.lpr:960-964).  Tiles of 8192 chunks: sizes, a block
 // exclusive scan, then every code is OR-ed into the zeroed word slab at its
 // bit offset (a code straddles at most two 32-bit words).
+// EMIT_CPS: also the decoder's seek-table checkpoints (gsc_decode.h).  Chunk
+// j's bit offset and `prev`, the vcbsCnt before it, are the decoder's
+// (bit offset, variableCodingHeader) on entry to symbol j, so for every
+// j % kDecodeS == 0 make_checkpoint(bit, prev) goes to cps[f.cp_off + j / kDecodeS].
+template <bool EMIT_CPS>
 __global__ __launch_bounds__(kPackThreads) void pack_kernel(PackFrame* __restrict__ frames, const int* __restrict__ best,
                                                             const int* __restrict__ remap, uint32_t* __restrict__ words,
-                                                            uint32_t* __restrict__ codes_out) {
+                                                            uint32_t* __restrict__ codes_out,
+                                                            uint64_t* __restrict__ cps) {
     __shared__ int wsum[kPackThreads / 64];
     __shared__ int carry;
     __shared__ int overrun;
@@ -93,6 +103,7 @@ __global__ __launch_bounds__(kPackThreads) void pack_kernel(PackFrame* __restric
         int size[kPackPerThread];
         int prev = -1;  // prevVcbsCnt (encoder.lpr:1058-1060)
         if (j0 >= 1 && j0 - 1 < N) prev = vc_of(rm[b[j0 - 1] >> 2]);
+        const int prev0 = prev;
         int sum = 0;
 #pragma unroll
         for (int e = 0; e < kPackPerThread; ++e) {
@@ -138,6 +149,8 @@ __global__ __launch_bounds__(kPackThreads) void pack_kernel(PackFrame* __restric
         int total = 0;
         for (int i = 0; i < kPackThreads / 64; ++i) total += wsum[i];
         int bit = carry + wbase + incl - sum;
+        if (EMIT_CPS && j0 < N && j0 % kDecodeS == 0)
+            cps[(int64_t)f.cp_off + j0 / kDecodeS] = make_checkpoint((uint64_t)bit, prev0);
 #pragma unroll
         for (int e = 0; e < kPackPerThread; ++e) {
             if (size[e] == 0) continue;
@@ -172,10 +185,17 @@ extern "C" hipError_t gsc_launch_usecount(const PackFrame* frames, int nframes, 
 }
 
 // words: the frames' slabs (capacity pack_word_capacity(N) each) must be zeroed;
-// codes (optional): N words per frame at out_off, final index << 2 | neg << 1 | rev
+// codes (optional): N words per frame at out_off, final index << 2 | neg << 1 | rev;
+// cps (optional): ceil(N / kDecodeS) seek-table checkpoints per frame at cp_off
 extern "C" hipError_t gsc_launch_pack(PackFrame* frames, int nframes, const int* best, const int* remap,
-                                      uint32_t* words, uint32_t* codes, hipStream_t st) {
+                                      uint32_t* words, uint32_t* codes, uint64_t* cps, hipStream_t st) {
     if (nframes <= 0) return hipSuccess;
-    hipLaunchKernelGGL(pack_kernel, dim3(nframes), dim3(kPackThreads), 0, st, frames, best, remap, words, codes);
+    if (cps) {
+        hipLaunchKernelGGL(pack_kernel<true>, dim3(nframes), dim3(kPackThreads), 0, st, frames, best, remap, words,
+                           codes, cps);
+    } else {
+        hipLaunchKernelGGL(pack_kernel<false>, dim3(nframes), dim3(kPackThreads), 0, st, frames, best, remap, words,
+                           codes, cps);
+    }
     return hipGetLastError();
 }

@@ -22,6 +22,7 @@
 
 #include "../../include/soundchunks.h"
 #include "fpc_math.h"
+#include "gsc_decode.h"
 #include "gsc_device.h"
 #include "gsc_encoder.h"
 
@@ -53,7 +54,7 @@ extern "C" hipError_t gsc_launch_sqdiff(const int16_t* a, const int16_t* b, int6
 extern "C" hipError_t gsc_launch_usecount(const gsc::PackFrame* frames, int nframes, const int* best, int* counts,
                                           hipStream_t st);
 extern "C" hipError_t gsc_launch_pack(gsc::PackFrame* frames, int nframes, const int* best, const int* remap,
-                                      uint32_t* words, uint32_t* codes, hipStream_t st);
+                                      uint32_t* words, uint32_t* codes, uint64_t* cps, hipStream_t st);
 extern "C" hipError_t gsc_launch_ann_build_many(const void* trees, int ntrees, hipStream_t st);
 extern "C" hipError_t gsc_launch_knnfit_ann(const void* trees, const void* jobs, int njobs, const float* q, int* out,
                                             float* pq_key, void* pq_node, int pq_cap, hipStream_t st);
@@ -706,6 +707,11 @@ struct PostCtx {
     DevBuf<uint32_t> dWords, dCodes;
     DevBuf<FitFrame> dFit;
     DevBuf<PackFrame> dPack;
+    // with a seek table: the packer's checkpoints, frame i's ceil(n / kDecodeS) at cpoff[i]
+    bool table = false;
+    std::vector<int64_t> cpoff;
+    DevBuf<uint64_t> dCps;
+    std::vector<uint64_t> hCps;
     DevArena ov_arena;  // KNNFit overflow replay scratch (kept until the encode is done)
     const float* dQry = nullptr;
     float* hCand = nullptr;
@@ -935,7 +941,7 @@ int Encoder::post_group(std::vector<FrameState>& frames, const std::vector<int>&
         const size_t i = size_t(ids[k]);
         const FrameState& f = frames[i];
         fit[size_t(k)] = FitFrame{c.coff[i], c.noff[i] * cs, c.noff[i], f.r, f.n, eps[size_t(k)], 0};
-        pk[size_t(k)] = PackFrame{c.noff[i], c.roff[i], c.woff[i], f.n, f.r, 0, 0};
+        pk[size_t(k)] = PackFrame{c.noff[i], c.roff[i], c.woff[i], f.n, f.r, 0, c.table ? int32_t(c.cpoff[i]) : 0};
         maxN = std::max(maxN, f.n);
         maxR = std::max(maxR, f.r);
     }
@@ -1050,7 +1056,7 @@ int Encoder::post_group(std::vector<FrameState>& frames, const std::vector<int>&
                  "remap upload");
     }
     ok = ok && chk(gsc_launch_pack(c.dPack.p + gb, g, c.dBest.p, c.dRemap.p, c.dWords.p, c.recon ? c.dCodes.p : nullptr,
-                                   st),
+                                   c.table ? c.dCps.p : nullptr, st),
                    "pack launch") &&
          chk(hipMemcpyAsync(pk.data(), c.dPack.p + gb, sizeof(PackFrame) * size_t(g), hipMemcpyDeviceToHost, st),
              "download") &&
@@ -1069,6 +1075,12 @@ int Encoder::post_group(std::vector<FrameState>& frames, const std::vector<int>&
             ok = chk(hipMemcpyAsync(c.hCodes + c.noff[i], c.dCodes.p + c.noff[i], sizeof(uint32_t) * size_t(frames[i].n),
                                     hipMemcpyDeviceToHost, st),
                      "code download");
+        const size_t ncp = c.table ? (size_t(frames[i].n) + kDecodeS - 1) / kDecodeS : 0;
+        if (ok && ncp)  // the checkpoints come down with the words
+            ok = chk(hipMemcpyAsync(c.hCps.data() + c.cpoff[i], c.dCps.p + c.cpoff[i], sizeof(uint64_t) * ncp,
+                                    hipMemcpyDeviceToHost, st),
+                     "checkpoint download");
+        frames[i].nbits = pk[size_t(k)].nbits;
     }
     if (!ok || !chk(hipStreamSynchronize(st), "stream download")) return -1;
     parallel_for(g, host_threads(), [&](int k) {
@@ -1125,7 +1137,7 @@ int Encoder::dsp_frame(int fi, int* atten_div, std::vector<float>* feat, std::st
 
 // ---- Encoder::encode_range: host srcData, device DSP + hot path ------------
 int Encoder::encode_range(int b, int e, std::vector<uint8_t>* out, std::string* err, gsc_timing* tim,
-                          ReconOut* recon, std::vector<size_t>* frame_bytes) {
+                          ReconOut* recon, std::vector<size_t>* frame_bytes, std::vector<uint8_t>* table) {
     if (ensure_device() != 0) {
         *err = t_err;
         return -1;
@@ -1179,7 +1191,9 @@ int Encoder::encode_range(int b, int e, std::vector<uint8_t>* out, std::string* 
     pc.roff.resize(size_t(nfr));
     pc.woff.resize(size_t(nfr));
     pc.noff.resize(size_t(nfr));
-    int64_t nc = 0, nr = 0, nw = 0, nn = 0;
+    pc.table = table != nullptr;
+    pc.cpoff.resize(size_t(nfr));
+    int64_t nc = 0, nr = 0, nw = 0, nn = 0, ncp = 0;
     for (int i = 0; i < nfr; ++i) {
         const int rmax = is_red[size_t(i)] ? K : frames[i].n;  // reducedChunks.Count before pruning
         pc.coff[size_t(i)] = nc;
@@ -1190,7 +1204,14 @@ int Encoder::encode_range(int b, int e, std::vector<uint8_t>* out, std::string* 
         nr += rmax;
         nw += pack_word_capacity(frames[i].n);
         nn += frames[i].n;
+        pc.cpoff[size_t(i)] = ncp;
+        ncp += (int64_t(frames[i].n) + kDecodeS - 1) / kDecodeS;
     }
+    if (pc.table && ncp >= (int64_t(1) << 31)) {
+        *err = "seek table: too many checkpoints for one call";
+        return -1;
+    }
+    if (pc.table) pc.hCps.resize(size_t(ncp));
     int64_t nred_pts = 0;
     for (int n : Ns) nred_pts += n;
     {
@@ -1205,6 +1226,7 @@ int Encoder::encode_range(int b, int e, std::vector<uint8_t>* out, std::string* 
             !chk(pc.dWords.alloc(size_t(nw)), "alloc") || !chk(pc.dFit.alloc(size_t(std::max(nfr, 1))), "alloc") ||
             !chk(pc.dPack.alloc(size_t(std::max(nfr, 1))), "alloc") ||
             (pc.recon && !chk(pc.dCodes.alloc(size_t(nn)), "alloc")) ||
+            (pc.table && !chk(pc.dCps.alloc(size_t(std::max<int64_t>(ncp, 1))), "alloc")) ||
             !chk(pa.cand.reserve(sizeof(float) * size_t(nc)), "pinned alloc") ||
             !chk(pa.cnt.reserve(sizeof(int) * size_t(nr)), "pinned alloc") ||
             !chk(pa.remap.reserve(sizeof(int) * size_t(nr)), "pinned alloc") ||
@@ -1351,6 +1373,21 @@ int Encoder::encode_range(int b, int e, std::vector<uint8_t>* out, std::string* 
         frame_bytes->clear();
         for (auto& f : frames) frame_bytes->push_back(f.stream.size());
     }
+    if (table) {
+        // the returned bytes as a stream of their own: offsets from their start.  Only the
+        // fields index_table_write reads are filled.
+        Index ix;
+        ix.frames.resize(frames.size());
+        size_t off = 0;
+        for (size_t i = 0; i < frames.size(); ++i) {
+            ix.frames[i].off = off;
+            ix.frames[i].nbits = uint64_t(frames[i].nbits);
+            off += frames[i].stream.size();
+        }
+        ix.len = off;
+        ix.cps = std::move(pc.hCps);
+        index_table_write(ix, table);
+    }
     double t4 = now_ms();
     if (std::getenv("GSC_HOST_TIMING"))
         std::fprintf(stderr,
@@ -1476,8 +1513,10 @@ int gsc_count_frames(const uint8_t* wav, size_t wav_len, const gsc_options* o, i
 // library-allocated buffer; timing lands in t_tim (host_prepare_ms excluded).
 // file_bytes: the range's bytes of every file of the batch; frame_bytes: each
 // frame's SaveStream bytes (frame_end - frame_begin entries)
+// table: the seek table of the returned bytes (with no frames in the range, of no stream: empty)
 static int encode_prepared(Encoder& enc, int frame_begin, int frame_end, uint8_t** out, size_t* out_len,
-                           size_t* file_bytes = nullptr, size_t* frame_bytes = nullptr) {
+                           size_t* file_bytes = nullptr, size_t* frame_bytes = nullptr,
+                           std::vector<uint8_t>* table = nullptr) {
     const double t0 = now_ms();
     const int fc = enc.frame_count();
     frame_begin = std::max(0, frame_begin);
@@ -1486,7 +1525,7 @@ static int encode_prepared(Encoder& enc, int frame_begin, int frame_end, uint8_t
     std::vector<size_t> fb;
     std::string err;
     if (frame_end > frame_begin) {
-        if (enc.encode_range(frame_begin, frame_end, &bytes, &err, &t_tim, nullptr, &fb) != 0) return fail(err);
+        if (enc.encode_range(frame_begin, frame_end, &bytes, &err, &t_tim, nullptr, &fb, table) != 0) return fail(err);
     }
     if (file_bytes) {
         const std::vector<int>& ff = enc.file_first();
@@ -1620,6 +1659,37 @@ int gsc_encode_prepared_frames(gsc_prepared* p, int frame_begin, int frame_end, 
     t_tim = gsc_timing{};
     if (encode_prepared(p->enc, frame_begin, frame_end, out, out_len, nullptr, frame_bytes) != 0) return -1;
     t_tim.host_prepare_ms = 0;  // paid once, in gsc_prepare
+    return 0;
+}
+
+int gsc_encode_prepared_with_table(gsc_prepared* p, int frame_begin, int frame_end, uint8_t** out, size_t* out_len,
+                                   uint8_t** table, size_t* table_len) {
+    if (!p || !out || !out_len || !table || !table_len) return fail("gsc_encode_prepared_with_table: null argument");
+    if (p->enc.file_first().size() != 2)
+        return fail("gsc_encode_prepared_with_table: a batch of files has no single table; index each file's bytes");
+    if (check_loaded(p, frame_begin, frame_end, "gsc_encode_prepared_with_table") != 0) return -1;
+    t_tim = gsc_timing{};
+    std::vector<uint8_t> t;
+    *table = static_cast<uint8_t*>(std::malloc(1));  // sized below; never NULL on success
+    if (!*table) return fail("out of host memory");
+    if (encode_prepared(p->enc, frame_begin, frame_end, out, out_len, nullptr, nullptr, &t) != 0) {
+        std::free(*table);
+        *table = nullptr;
+        return -1;
+    }
+    t_tim.host_prepare_ms = 0;  // paid once, in gsc_prepare
+    if (!t.empty()) {
+        uint8_t* q = static_cast<uint8_t*>(std::realloc(*table, t.size()));
+        if (!q) {
+            std::free(*table);
+            std::free(*out);
+            *table = *out = nullptr;
+            return fail("out of host memory");
+        }
+        std::memcpy(q, t.data(), t.size());
+        *table = q;
+    }
+    *table_len = t.size();
     return 0;
 }
 

@@ -37,12 +37,18 @@ class Index:
     """The host index of one ``.gsc`` stream (``gsc_index``): per frame the
     byte offset, FrameLength, ChunkSize, ChunkCount and first sample."""
 
-    def __init__(self, gsc: bytes, _handle=None):
+    def __init__(self, gsc: bytes, _handle=None, table: bytes | None = None):
         lib = _lib.load()
         self.gsc = gsc
         self._arr, self._ptr = _u8(gsc)
         self._owned = _handle is None  # a resident stream's index belongs to the stream
-        h = lib.gsc_index_create(self._ptr, len(self._arr)) if _handle is None else _handle
+        if _handle is not None:
+            h = _handle
+        elif table is None:
+            h = lib.gsc_index_create(self._ptr, len(self._arr))
+        else:  # no host walk: the table is checked against the stream on the device
+            tarr, tptr = _u8(table)
+            h = lib.gsc_index_create_with_table(self._ptr, len(self._arr), tptr, len(tarr))
         if not h:
             raise _lib.GscError(lib.gsc_last_error().decode(errors="replace"))
         self._h = h
@@ -68,6 +74,19 @@ class Index:
         _lib.check(lib.gsc_decode_indexed(self._ptr, len(self._arr), self._h, frame_begin, frame_end,
                                           ctypes.byref(pcm), ctypes.byref(n)))
         return _take(lib, pcm, n.value).reshape(-1, self.channels)
+
+    def table(self) -> bytes:
+        """The stream's seek table (layout: include/soundchunks.h): frame
+        offsets, bit counts and checkpoints, so that a later ``Decoder.index``,
+        ``open`` or ``decode`` of the same bytes needs no host walk.  Host only."""
+        lib = _lib.load()
+        out = ctypes.POINTER(ctypes.c_uint8)()
+        n = ctypes.c_size_t(0)
+        _lib.check(lib.gsc_index_table(self._h, ctypes.byref(out), ctypes.byref(n)))
+        try:
+            return ctypes.string_at(out, n.value)
+        finally:
+            lib.gsc_free(out)
 
     def locate(self, sample: int):
         """(frame, symbol row, position inside the chunk, checkpoint) of a
@@ -96,10 +115,14 @@ class ResidentStream:
     uploaded once by ``Decoder.open``; sample ranges then decode without
     touching the bytes again (``decode_samples``, ``Decoder.decode_crops``)."""
 
-    def __init__(self, gsc: bytes):
+    def __init__(self, gsc: bytes, table: bytes | None = None):
         lib = _lib.load()
         arr, ptr = _u8(gsc)
-        h = lib.gsc_stream_open(ptr, len(arr))
+        if table is None:
+            h = lib.gsc_stream_open(ptr, len(arr))
+        else:
+            tarr, tptr = _u8(table)
+            h = lib.gsc_stream_open_with_table(ptr, len(arr), tptr, len(tarr))
         if not h:
             raise _lib.GscError(lib.gsc_last_error().decode(errors="replace"))
         self._h = h
@@ -148,16 +171,26 @@ class Decoder:
     """GSCUnpack: .gsc bytes -> 16-bit PCM, bit-identical to the reference decoder."""
 
     @staticmethod
-    def index(gsc: bytes) -> Index:
-        return Index(gsc)
+    def index(gsc: bytes, table: bytes | None = None) -> Index:
+        """The stream's index: by the host walk, or from a seek table
+        (``Index.table()``, ``Encoder.encode(..., with_table=True)``), which is
+        checked on the device; a table that is not the stream's own raises."""
+        return Index(gsc, table=table)
 
     @staticmethod
     def checkpoint_symbols() -> int:
         return _lib.load().gsc_decode_checkpoint_symbols()
 
     @staticmethod
-    def open(gsc: bytes) -> ResidentStream:
-        return ResidentStream(gsc)
+    def open(gsc: bytes, table: bytes | None = None) -> ResidentStream:
+        return ResidentStream(gsc, table)
+
+    @staticmethod
+    def last_open_timing() -> dict:
+        """Where the last ``open`` / ``index(gsc, table)`` of this thread spent its time."""
+        t = _lib.GscOpenTiming()
+        _lib.load().gsc_last_open_timing(ctypes.byref(t))
+        return {k: getattr(t, k) for k, _ in t._fields_}
 
     CROP_VARIANTS = ("global", "lds", "fused")
 
@@ -216,11 +249,12 @@ class Decoder:
                                             ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream), written))
         return out, [int(written[i]) for i in range(len(crops))]
 
-    def decode(self, gsc: bytes, frame_begin: int = 0, frame_end: int = -1):
-        """(int16 array [n, channels], sample_rate) of frames [frame_begin, frame_end)."""
+    def decode(self, gsc: bytes, frame_begin: int = 0, frame_end: int = -1, table: bytes | None = None):
+        """(int16 array [n, channels], sample_rate) of frames [frame_begin, frame_end).
+        With a seek table the index comes from it instead of the host walk."""
         lib = _lib.load()
-        if frame_begin != 0 or frame_end != -1:
-            ix = Index(gsc)
+        if frame_begin != 0 or frame_end != -1 or table is not None:
+            ix = Index(gsc, table=table)
             try:
                 return ix.decode(frame_begin, frame_end), ix.sample_rate
             finally:

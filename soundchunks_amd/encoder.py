@@ -52,8 +52,16 @@ class Encoder:
         _lib.check(lib.gsc_count_frames(ptr, len(arr), ctypes.byref(self.options), ctypes.byref(n)))
         return n.value
 
-    def encode(self, wav: bytes, frame_begin: int = 0, frame_end: int = -1) -> bytes:
-        """Encode frames [frame_begin, frame_end) (default: all) to .gsc bytes."""
+    def encode(self, wav: bytes, frame_begin: int = 0, frame_end: int = -1, with_table: bool = False):
+        """Encode frames [frame_begin, frame_end) (default: all) to .gsc bytes;
+        with_table: (.gsc bytes, their seek table for ``Decoder.open`` /
+        ``index`` / ``decode``), the checkpoints straight from the index packer."""
+        if with_table:
+            p = self.prepare(wav)
+            try:
+                return p.encode(frame_begin, frame_end, with_table=True)
+            finally:
+                p.close()
         lib = _lib.load()
         arr, ptr = _u8(wav)
         out = ctypes.POINTER(ctypes.c_uint8)()
@@ -154,10 +162,22 @@ class Prepared:
         _lib.check(_lib.load().gsc_prepared_frame_bounds(self._h, _ip(st), _ip(en)))
         return st[: self.frame_count], en[: self.frame_count]
 
-    def encode(self, frame_begin: int = 0, frame_end: int = -1) -> bytes:
+    def encode(self, frame_begin: int = 0, frame_end: int = -1, with_table: bool = False):
+        """.gsc bytes of frames [frame_begin, frame_end); with_table: (bytes,
+        the seek table of those bytes, a stream of their own)."""
         lib = _lib.load()
         out = ctypes.POINTER(ctypes.c_uint8)()
         n = ctypes.c_size_t(0)
+        if with_table:
+            tab = ctypes.POINTER(ctypes.c_uint8)()
+            tn = ctypes.c_size_t(0)
+            _lib.check(lib.gsc_encode_prepared_with_table(self._h, frame_begin, frame_end, ctypes.byref(out),
+                                                          ctypes.byref(n), ctypes.byref(tab), ctypes.byref(tn)))
+            try:
+                return ctypes.string_at(out, n.value), ctypes.string_at(tab, tn.value)
+            finally:
+                lib.gsc_free(out)
+                lib.gsc_free(tab)
         _lib.check(lib.gsc_encode_prepared(self._h, frame_begin, frame_end, ctypes.byref(out), ctypes.byref(n)))
         try:
             return ctypes.string_at(out, n.value)
