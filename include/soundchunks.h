@@ -355,6 +355,62 @@ typedef struct {
 } gsc_open_timing;
 void gsc_last_open_timing(gsc_open_timing *t);
 
+/* ---- stream sets: many streams opened as one ---------------------------------- */
+/* A loader's corpus is thousands of short files.  gsc_stream_set_open opens
+ * `count` streams as one resident set: one set of slabs holds every stream's
+ * bytes, checkpoints, int16 codebooks, attenuations and frame table, back to
+ * back.  tables may be NULL (every stream is walked on the host); tables[i] may
+ * be NULL (stream i is walked).  Stream i with tables[i] is accepted and
+ * refused exactly as gsc_stream_open_with_table(gscs[i], tables[i]) would be.
+ * The streams are indexed in parallel on the host; only the raw bytes, the
+ * checkpoints and the frame descriptors are uploaded, and one kernel launch
+ * expands every frame's codebook and attenuations on the device, one more
+ * checks every table.  The number of device allocations, launches and
+ * synchronisations does not depend on `count`, the number of copies only on
+ * the bytes; the work runs on the default stream and the call waits for that
+ * stream, once, never for the device.  A refusal fails the whole call
+ * and frees everything: NULL and gsc_last_error, "stream <i>: " followed by
+ * that stream's own message, i the lowest refused stream (a stream the host
+ * refuses is reported before one only the device check refuses).  count <= 0
+ * and 2^31 or more frames or checkpoints in all are refused.
+ *
+ * A member is an ordinary gsc_stream, borrowed from the set and valid until
+ * gsc_stream_set_free: gsc_stream_info, _index, _device, _decode_samples and
+ * gsc_decode_crops take it, and one gsc_decode_crops call may mix members of
+ * several sets and streams opened on their own.  gsc_stream_free on a member
+ * frees nothing and sets gsc_last_error.  A member's index keeps no host copy
+ * of its codebooks; gsc_decode_indexed builds one on first use. */
+typedef struct gsc_stream_set gsc_stream_set;
+gsc_stream_set *gsc_stream_set_open(const uint8_t *const *gscs, const size_t *lens, const uint8_t *const *tables,
+                                    const size_t *table_lens, int count);
+int gsc_stream_set_count(const gsc_stream_set *set);
+gsc_stream *gsc_stream_set_stream(gsc_stream_set *set, int i);
+/* waits for the device's queued work first, as gsc_stream_free */
+void gsc_stream_set_free(gsc_stream_set *set);
+/* Timing of the last gsc_stream_set_open on the calling thread (milliseconds):
+ * host_ms the indexes and the layout, upload_ms allocation, staging and copies
+ * (host clock), expand_ms and verify_ms the two kernels (device events).  The
+ * last four fields count runtime calls where they are made. */
+typedef struct {
+    double host_ms, upload_ms, expand_ms, verify_ms, total_ms;
+    long long uploaded_bytes, streams, frames, checkpoints;
+    int device_allocations, h2d_copies, launches, synchronisations;
+} gsc_set_open_timing;
+void gsc_last_set_open_timing(gsc_set_open_timing *t);
+/* Stage entry point, parity tests: the device tables of one frame of a
+ * resident stream (a set's member or not), downloaded: ChunkCount * ChunkSize
+ * int16 rounded up to a multiple of 8 (the padding is zero) to cb_out,
+ * ChunkCount attenuations to att_out. */
+int gsc_stream_tables(const gsc_stream *st, int frame, int16_t *cb_out, uint8_t *att_out);
+/* gsc_encode_prepared_files that also returns every file's seek table:
+ * tables_len bytes in *tables (release with gsc_free), table_bytes[i] of them
+ * file i's, in file order.  Each is the table of that file's returned bytes,
+ * cut from the packer's checkpoints and rebased to the file's first byte; a
+ * file with no frame in the range gets an empty table. */
+int gsc_encode_prepared_files_with_tables(gsc_prepared *p, int frame_begin, int frame_end, uint8_t **out,
+                                          size_t *out_len, size_t *file_bytes, uint8_t **tables, size_t *tables_len,
+                                          size_t *table_bytes);
+
 /* Timing of the last gsc_decode*, gsc_stream_open or crop call on the calling
  * thread (milliseconds).  h2d_bytes: the bytes that call uploaded. */
 typedef struct {

@@ -91,6 +91,26 @@ class GscOpenTiming(ctypes.Structure):
     ]
 
 
+class GscSetOpenTiming(ctypes.Structure):
+    """Mirror of ``gsc_set_open_timing``."""
+
+    _fields_ = [
+        ("host_ms", ctypes.c_double),
+        ("upload_ms", ctypes.c_double),
+        ("expand_ms", ctypes.c_double),
+        ("verify_ms", ctypes.c_double),
+        ("total_ms", ctypes.c_double),
+        ("uploaded_bytes", ctypes.c_longlong),
+        ("streams", ctypes.c_longlong),
+        ("frames", ctypes.c_longlong),
+        ("checkpoints", ctypes.c_longlong),
+        ("device_allocations", ctypes.c_int),
+        ("h2d_copies", ctypes.c_int),
+        ("launches", ctypes.c_int),
+        ("synchronisations", ctypes.c_int),
+    ]
+
+
 class GscCrop(ctypes.Structure):
     """Mirror of ``gsc_crop``: per-channel sample positions of one stream."""
 
@@ -173,6 +193,15 @@ SIGNATURES = {
     "gsc_index_create_with_table": (ctypes.c_void_p, [_U8P, ctypes.c_size_t, _U8P, ctypes.c_size_t]),
     "gsc_stream_open_with_table": (ctypes.c_void_p, [_U8P, ctypes.c_size_t, _U8P, ctypes.c_size_t]),
     "gsc_last_open_timing": (None, [ctypes.POINTER(GscOpenTiming)]),
+    "gsc_stream_set_open": (ctypes.c_void_p, [ctypes.POINTER(_U8P), _SZP, ctypes.POINTER(_U8P), _SZP, ctypes.c_int]),
+    "gsc_stream_set_count": (ctypes.c_int, [ctypes.c_void_p]),
+    "gsc_stream_set_stream": (ctypes.c_void_p, [ctypes.c_void_p, ctypes.c_int]),
+    "gsc_stream_set_free": (None, [ctypes.c_void_p]),
+    "gsc_last_set_open_timing": (None, [ctypes.POINTER(GscSetOpenTiming)]),
+    "gsc_stream_tables": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, _I16P, _U8P]),
+    "gsc_encode_prepared_files_with_tables": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
+                                                             ctypes.POINTER(_U8P), _SZP, _SZP, ctypes.POINTER(_U8P),
+                                                             _SZP, _SZP]),
     "gsc_decode_checkpoint_symbols": (ctypes.c_int, []),
     "gsc_index_locate": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_longlong, _IP, _LLP, _IP, _LLP]),
     "gsc_stream_open": (ctypes.c_void_p, [_U8P, ctypes.c_size_t]),

@@ -85,6 +85,7 @@ struct Index {
     int64_t samples = 0;            // per channel
     int64_t symbols = 0;
     size_t len = 0;                 // bytes of the stream the index was built from
+    bool has_tables = true;         // false: codebook and att are empty until index_expand_tables
 };
 
 // The sequential pass (host only): frame offsets, checkpoints, lookup tables,
@@ -112,8 +113,23 @@ using ParallelRunner = std::function<void(int n, const std::function<void(int)>&
 // and bit counts are the stream's own is left to decode_verify_kernel
 // (gsc_decode.hip); an index from here must not be used before that passed.
 // 0, or -1 with *err set; never reads outside [g, g + len) or the table.
+// expand = false leaves codebook and att empty (has_tables false): a stream
+// set expands them on the device, the host only on demand.
 int index_from_table(const uint8_t* g, size_t len, const uint8_t* table, size_t tlen, Index* ix, std::string* err,
-                     const ParallelRunner* par = nullptr);
+                     const ParallelRunner* par = nullptr, bool expand = true);
+
+// codebook and att of an index that has none (has_tables false), from the
+// stream it was built from, as the walk fills them; nothing when it has them.
+void index_expand_tables(const uint8_t* g, Index* ix);
+// the reverse: an index gives up its host copy of the tables
+void index_drop_tables(Index* ix);
+
+// The table of stream g (index_from_table's host checks apply) cut into the
+// tables of nparts consecutive pieces of part_bytes[i] bytes, each a stream of
+// its own whose frames start at its first byte; an empty piece gets an empty
+// table.  0, or -1 with *err set.
+int index_table_split(const uint8_t* g, size_t len, const uint8_t* table, size_t tlen, const size_t* part_bytes,
+                      int nparts, std::vector<std::vector<uint8_t>>* out, std::string* err);
 
 // ---- decode_verify_kernel's report -----------------------------------------
 // One status word: kVerifyOk, or the smallest failing checkpoint (counted over
@@ -141,6 +157,50 @@ int index_locate(const Index& ix, int64_t sample, int* frame, int64_t* row, int*
 struct ResFrame : FrameTables {
     int64_t first_sample;  // per channel
 };
+
+// ---- slabs: streams and frame ranges back to back on the device -------------
+// A position in, or a length of, each of the four slabs: stream bytes,
+// checkpoints, codebook int16 and attenuation bytes.
+struct SlabPos {
+    int64_t bytes = 0, cps = 0, cb = 0, att = 0;
+};
+inline SlabPos operator+(const SlabPos& a, const SlabPos& b) {
+    return {a.bytes + b.bytes, a.cps + b.cps, a.cb + b.cb, a.att + b.att};
+}
+inline SlabPos operator-(const SlabPos& a, const SlabPos& b) {
+    return {a.bytes - b.bytes, a.cps - b.cps, a.cb - b.cb, a.att - b.att};
+}
+// What frames [b, e) of a stream occupy of its bytes and of its index's arrays.
+struct Span {
+    SlabPos first, count;
+};
+Span span_of(const Index& ix, int b, int e);
+// The device descriptor of a frame whose stream was uploaded so that position
+// p of the stream lies at rebase + p of the slabs.
+FrameTables frame_tables(const IndexFrame& f, const SlabPos& rebase);
+
+// Where expand_tables_kernel (gsc_decode.hip) finds a frame's packed tables in
+// the byte slab: the attenuation nibbles, the codebook codes, ChunkBitDepth.
+struct TableSrc {
+    int64_t att_byte, cb_byte;
+    int32_t bd, pad_;
+};
+
+// A stream set (gsc_stream_set_open): every stream whole, back to back in one
+// set of slabs, as decode_parts lays out its parts.  Host only.
+struct SetLayout {
+    std::vector<SlabPos> base;    // where stream i starts in the slabs
+    std::vector<int64_t> frame0;  // stream i's first frame in `frames`; count + 1 entries
+    SlabPos total;
+    std::vector<ResFrame> frames;  // every frame of every stream, rebased
+    std::vector<TableSrc> src;     // per frame
+    std::vector<uint64_t> bits;    // per frame: the bits of its bitstream
+};
+// Refuses (-1, *err) count <= 0 and 2^31 or more frames or checkpoints in all.
+int set_layout(const Index* const* ixs, int count, SetLayout* out, std::string* err);
+// The stream that owns checkpoint c of the set's checkpoint slab (a status word
+// of decode_verify_kernel >> 8): the last one with base.cps <= c.
+int set_stream_of_checkpoint(const SetLayout& lay, int64_t c);
 
 // One crop on the device: its stream's slabs and their sizes, the clipped
 // sample range, the frames [f0, f1) it crosses and its first piece.

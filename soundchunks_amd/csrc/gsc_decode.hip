@@ -9,6 +9,10 @@
 //   decode_verify_kernel  the same lanes and the same walk (walk_segment,
 //                         gsc_decode_device.h) over a claimed seek table:
 //                         nothing is written but one status word
+//   expand_tables_kernel  one lane per 8 codebook values: a stream set's packed
+//                         codebook codes and attenuation nibbles, already in
+//                         the byte slab, to the int16 and byte tables the
+//                         other kernels read (decoder.lpr:115-158)
 //   decode_synth_kernel   one lane per output sample: the low 16 bits of
 //                         (CAttrLookup[neg][att[idx]] * chunk[idx][j']) >> 15
 //                         in 32-bit arithmetic (the reference wraps, it does
@@ -89,6 +93,74 @@ __global__ __launch_bounds__(kUnpackThreads) void decode_verify_kernel(const Res
     if (reason) atomicMin(status, (unsigned long long)c << 8 | (unsigned long long)reason);
 }
 
+// A byte of the byte slab; zero outside it.
+__device__ __forceinline__ int slab_byte(const uint8_t* __restrict__ bytes, int64_t nbytes, int64_t i) {
+    return i >= 0 && i < nbytes ? (int)bytes[i] : 0;
+}
+
+// The tables of every frame of a stream set in one launch, value for value
+// what frame_tables_expand (gsc_decode_index.cpp) writes on the host.  A
+// frame's codebook occupies a multiple of 8 int16 from a cb_off that is a
+// multiple of 8, so group g of 8 values belongs to one frame: the last one
+// whose cb_off is <= 8 g (a frame without a codebook owns no group).  The lane
+// writes the group with one 16-byte store, values past count * cs as zero, and
+// attenuations [8 l, 8 l + 8) of its frame when l is its group within the
+// frame: there are at least count / 8 groups, so every attenuation is written.
+//   8 bit:  (b - 128) * 2047 / 127, truncated toward zero
+//   12 bit: 3 bytes b0 b1 b2 -> (b1 | (b0 & 0xf0) << 4) - 2048, (b2 | (b0 & 0x0f) << 8) - 2048;
+//           an odd ChunkSize ends each chunk with 2 bytes for one value
+//   attenuations: high nibble first
+// Cost accepted: every lane runs its own binary search over the frame table in
+// global memory, and the 12-bit path divides a 64-bit index per value; the
+// whole launch is 0.02 ms for 1024 streams, 1 % of an open.
+__global__ __launch_bounds__(kUnpackThreads) void expand_tables_kernel(const ResFrame* __restrict__ frames,
+                                                                       const TableSrc* __restrict__ src, int nframes,
+                                                                       int64_t ngroups,
+                                                                       const uint8_t* __restrict__ bytes,
+                                                                       int64_t nbytes, int16_t* __restrict__ cb,
+                                                                       int64_t ncb, uint8_t* __restrict__ att,
+                                                                       int64_t natt) {
+    const int64_t g = (int64_t)blockIdx.x * kUnpackThreads + threadIdx.x;
+    if (g >= ngroups) return;
+    const int fi = last_le(0, nframes - 1, g * 8, [&](int i) { return frames[i].cb_off; });
+    const ResFrame& f = frames[fi];
+    const TableSrc s = src[fi];
+    const int cs = f.cs, count = f.count;
+    const int64_t e0 = g * 8 - f.cb_off;  // the group's first value within the frame
+    if (cs <= 0 || count <= 0 || e0 < 0 || (f.cb_off & 7) != 0) return;
+    const int64_t n = (int64_t)count * cs;
+    const int chunk_bytes = (cs / 2) * 3 + (cs & 1) * 2;
+    uint32_t w[4] = {0u, 0u, 0u, 0u};  // the 8 values, two per word, low half first
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        const int64_t e = e0 + k;
+        int val = 0;
+        if (e < n) {
+            if (s.bd == 8) {
+                val = (slab_byte(bytes, nbytes, s.cb_byte + e) - 128) * 2047 / 127;
+            } else {
+                const int64_t i = e / cs;
+                const int j = (int)(e - i * cs);
+                const int64_t p = s.cb_byte + i * chunk_bytes + (j / 2) * 3;
+                const int b = slab_byte(bytes, nbytes, p);
+                val = (j & 1) ? (slab_byte(bytes, nbytes, p + 2) | (b & 0x0f) << 8) - 2048
+                              : (slab_byte(bytes, nbytes, p + 1) | (b & 0xf0) << 4) - 2048;
+            }
+        }
+        w[k >> 1] |= (uint32_t)(uint16_t)(int16_t)val << (16 * (k & 1));
+    }
+    const int64_t o = f.cb_off + e0;
+    if (o + 8 <= ncb) *reinterpret_cast<uint4*>(cb + o) = make_uint4(w[0], w[1], w[2], w[3]);
+    const int64_t a0 = e0;  // 8 (e0 / 8): this lane's attenuations
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        const int64_t a = a0 + k, ai = f.att_off + a;
+        if (a >= count || ai < 0 || ai >= natt) continue;
+        const int b = slab_byte(bytes, nbytes, s.att_byte + a / 2);
+        att[ai] = (uint8_t)((a & 1) ? b & 0x0f : b >> 4);
+    }
+}
+
 __global__ __launch_bounds__(kDecodeSynthThreads) void decode_synth_kernel(
     const DecFrame* __restrict__ frames, int nframes, const DecJob* __restrict__ jobs, int njobs, int lds_bytes,
     const uint16_t* __restrict__ sym, int64_t nsym, const int16_t* __restrict__ cb, int64_t ncb,
@@ -137,14 +209,32 @@ extern "C" hipError_t gsc_launch_decode_unpack(const DecFrame* frames, int nfram
     return hipGetLastError();
 }
 
-// *status must hold kVerifyOk; frame_bits: the claimed bit count of every frame
+// *status must hold kVerifyOk; frame_bits: the claimed bit count of every frame; *launched (may be
+// null) is incremented when a kernel is launched
 extern "C" hipError_t gsc_launch_decode_verify(const ResFrame* frames, const uint64_t* frame_bits, int nframes,
                                                const uint64_t* cps, int64_t ncp, const uint32_t* words, int64_t nwords,
-                                               unsigned long long* status, hipStream_t st) {
+                                               unsigned long long* status, hipStream_t st, int* launched) {
     if (nframes <= 0 || ncp <= 0) return hipSuccess;
     const unsigned grid = (unsigned)((ncp + kUnpackThreads - 1) / kUnpackThreads);
     hipLaunchKernelGGL(decode_verify_kernel, dim3(grid), dim3(kUnpackThreads), 0, st, frames, frame_bits, nframes, cps,
                        ncp, words, nwords, status);
+    if (launched) ++*launched;
+    return hipGetLastError();
+}
+
+// Writes the codebook of every frame (its padding included) and every
+// attenuation; the slabs' zero tails are the allocation's.  *launched (may be
+// null) is incremented when the kernel is launched.
+extern "C" hipError_t gsc_launch_expand_tables(const ResFrame* frames, const TableSrc* src, int nframes, int64_t ncb_used,
+                                               const uint8_t* bytes, int64_t nbytes, int16_t* cb, int64_t ncb,
+                                               uint8_t* att, int64_t natt, hipStream_t st, int* launched) {
+    const int64_t ngroups = ncb_used / 8;
+    if (nframes <= 0 || ngroups <= 0) return hipSuccess;
+    if (ngroups > (int64_t(1) << 31) * kUnpackThreads - 1) return hipErrorInvalidValue;
+    const unsigned grid = (unsigned)((ngroups + kUnpackThreads - 1) / kUnpackThreads);
+    hipLaunchKernelGGL(expand_tables_kernel, dim3(grid), dim3(kUnpackThreads), 0, st, frames, src, nframes, ngroups,
+                       bytes, nbytes, cb, ncb, att, natt);
+    if (launched) ++*launched;
     return hipGetLastError();
 }
 

@@ -5,8 +5,10 @@
 // gsc_decode.hip's two stages over all of them.  A resident stream
 // (gsc_stream_open, gsc_stream_open_with_table) keeps the index and the bytes on the
 // device; gsc_decode_crops then decodes batches of sample ranges into
-// caller-owned device memory (plan_crops; gsc_decode_crops.hip).  Both keep
-// their device copies in a Slabs and describe a frame with frame_tables.
+// caller-owned device memory (plan_crops; gsc_decode_crops.hip).  A stream set
+// (gsc_stream_set_open) keeps many streams in one Slabs, laid out by
+// set_layout (gsc_decode_set.cpp), their tables expanded on the device.  All
+// keep their device copies in a Slabs and describe a frame with frame_tables.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -14,6 +16,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <memory>
+#include <mutex>
 
 #include "../../include/soundchunks.h"
 #include "gsc_decode.h"
@@ -29,7 +32,12 @@ extern "C" hipError_t gsc_launch_decode_synth(const gsc::DecFrame* frames, int n
 
 extern "C" hipError_t gsc_launch_decode_verify(const gsc::ResFrame* frames, const uint64_t* frame_bits, int nframes,
                                                const uint64_t* cps, int64_t ncp, const uint32_t* words, int64_t nwords,
-                                               unsigned long long* status, hipStream_t st);
+                                               unsigned long long* status, hipStream_t st, int* launched = nullptr);
+
+extern "C" hipError_t gsc_launch_expand_tables(const gsc::ResFrame* frames, const gsc::TableSrc* src, int nframes,
+                                               int64_t ncb_used, const uint8_t* bytes, int64_t nbytes, int16_t* cb,
+                                               int64_t ncb, uint8_t* att, int64_t natt, hipStream_t st,
+                                               int* launched);
 
 extern "C" hipError_t gsc_launch_crop_unpack(const gsc::CropJob* jobs, int ncrops, const gsc::CropPiece* pieces,
                                              int npieces, uint16_t* sym, int64_t nslots, hipStream_t st);
@@ -42,6 +50,7 @@ extern "C" hipError_t gsc_launch_crop_fused(const gsc::CropJob* jobs, int ncrops
 
 struct gsc_index {
     gsc::Index ix;
+    std::mutex mu;  // a set member's host tables are filled on first use (ensure_tables)
 };
 
 namespace gsc {
@@ -56,6 +65,9 @@ namespace {
 
 thread_local gsc_decode_timing t_dtim;
 thread_local gsc_open_timing t_otim;  // the last gsc_stream_open* / gsc_index_create_with_table
+thread_local gsc_set_open_timing t_stim;  // the last gsc_stream_set_open
+// where Dev::alloc counts its hipMalloc calls while a stream set opens (else null)
+thread_local int* t_alloc_count = nullptr;
 // crop decode: 0 unpack, then synthesis with the codebook from global memory; 1 the same with the codebook
 // staged in LDS; 2 unpack and synthesis fused in one launch (DESIGN.md "f5 decoder" has the A/B)
 thread_local int t_crop_variant = 2;
@@ -76,7 +88,10 @@ struct Dev {
     ~Dev() {
         if (p) (void)hipFree(p);
     }
-    hipError_t alloc(size_t n) { return hipMalloc(reinterpret_cast<void**>(&p), sizeof(T) * std::max<size_t>(n, 1)); }
+    hipError_t alloc(size_t n) {
+        if (t_alloc_count) ++*t_alloc_count;
+        return hipMalloc(reinterpret_cast<void**>(&p), sizeof(T) * std::max<size_t>(n, 1));
+    }
 };
 
 struct Event {
@@ -85,50 +100,6 @@ struct Event {
         if (e) (void)hipEventDestroy(e);
     }
 };
-
-// A position in, or a length of, each of the four slabs: stream bytes,
-// checkpoints, codebook int16 and attenuation bytes.
-struct SlabPos {
-    int64_t bytes = 0, cps = 0, cb = 0, att = 0;
-};
-SlabPos operator+(const SlabPos& a, const SlabPos& b) {
-    return {a.bytes + b.bytes, a.cps + b.cps, a.cb + b.cb, a.att + b.att};
-}
-SlabPos operator-(const SlabPos& a, const SlabPos& b) {
-    return {a.bytes - b.bytes, a.cps - b.cps, a.cb - b.cb, a.att - b.att};
-}
-
-// What frames [b, e) of a stream occupy of its bytes and of its index's arrays.
-struct Span {
-    SlabPos first, count;
-};
-Span span_of(const Index& ix, int b, int e) {
-    if (b >= e) return Span{};
-    const IndexFrame& fb = ix.frames[size_t(b)];
-    const IndexFrame& fe = ix.frames[size_t(e) - 1];
-    const SlabPos first{int64_t(fb.off), int64_t(fb.cp_first), int64_t(fb.cb_first), int64_t(fb.att_first)};
-    const SlabPos end{int64_t(fe.end_off), int64_t(fe.cp_first + fe.cp_count),
-                      int64_t(fe.cb_first + ((size_t(fe.count) * size_t(fe.cs) + 7) & ~size_t(7))),
-                      int64_t(fe.att_first + size_t(fe.count))};
-    return Span{first, end - first};
-}
-
-// The device descriptor of a frame whose stream was uploaded so that position
-// p of the stream lies at rebase + p of the slabs.
-FrameTables frame_tables(const IndexFrame& f, const SlabPos& rebase) {
-    FrameTables d{};
-    d.bs_off = rebase.bytes + int64_t(f.bs_off);
-    d.cb_off = rebase.cb + int64_t(f.cb_first);
-    d.att_off = rebase.att + int64_t(f.att_first);
-    d.nsym = f.nsym;
-    d.cp_first = rebase.cps + int64_t(f.cp_first);
-    d.ver = f.ver;
-    d.ch = f.ch;
-    d.cs = f.cs;
-    d.count = f.count;
-    std::memcpy(d.lut, f.lut, sizeof(d.lut));
-    return d;
-}
 
 // the dynamic LDS a synthesis workgroup wants for a frame: its staged tables when they fit
 int frame_lds_bytes(const IndexFrame& f) {
@@ -187,6 +158,20 @@ struct Slabs {
         return 0;
     }
 };
+
+// n bytes of host staging to the device in pieces of at most kStagePiece: the
+// number of copies follows the bytes, not the streams they came from.
+constexpr size_t kStagePiece = size_t(64) << 20;
+int copy_pieces(void* dst, const void* src, size_t n, hipStream_t st, gsc_set_open_timing* tim) {
+    for (size_t at = 0; at < n; at += kStagePiece) {
+        const size_t m = std::min(kStagePiece, n - at);
+        DEC_TRY(hipMemcpyAsync(static_cast<unsigned char*>(dst) + at, static_cast<const unsigned char*>(src) + at, m,
+                               hipMemcpyHostToDevice, st));
+        ++tim->h2d_copies;
+        tim->uploaded_bytes += (long long)m;
+    }
+    return 0;
+}
 
 // frames [b, e) of one stream
 struct Part {
@@ -311,10 +296,47 @@ struct gsc_stream {
     gsc_index idx;
     int device = 0;
     int lds_bytes = 0;  // the largest staged codebook + attenuations of a frame
+    gsc::Slabs<gsc::ResFrame> slabs;  // its own; empty in a member of a set
+    // what the kernels get: its own slabs, or the set's with `frames` at its own first frame
+    const gsc::ResFrame* frames = nullptr;
+    const uint64_t* cps = nullptr;
+    const uint32_t* words = nullptr;
+    const int16_t* cb = nullptr;
+    const uint8_t* att = nullptr;
+    int64_t ncp = 0, nwords = 0, ncb = 0, natt = 0;
+    const gsc_stream_set* set = nullptr;  // the owner of a borrowed member
+
+    void view(const gsc::Slabs<gsc::ResFrame>& s, int64_t frame0) {
+        frames = s.frames.p + frame0;
+        cps = s.cps.p;
+        words = s.words();
+        cb = s.cb.p;
+        att = s.att.p;
+        ncp = s.ncp;
+        nwords = s.nwords;
+        ncb = s.ncb;
+        natt = s.natt;
+    }
+};
+
+// Streams opened together: one set of slabs, one index and one borrowed
+// gsc_stream per member.
+struct gsc_stream_set {
+    int device = 0;
     gsc::Slabs<gsc::ResFrame> slabs;
+    std::unique_ptr<gsc_stream[]> members;
+    int count = 0;
 };
 
 using namespace gsc;
+
+// The index of a set's member holds no codebook and no attenuations until a
+// whole-frame decode asks for them (decode_parts uploads them from the host).
+static void ensure_tables(const gsc_index* ix, const uint8_t* gsc) {
+    gsc_index* m = const_cast<gsc_index*>(ix);
+    std::lock_guard<std::mutex> lock(m->mu);
+    index_expand_tables(gsc, &m->ix);
+}
 
 extern "C" {
 
@@ -364,6 +386,7 @@ int gsc_decode_indexed(const uint8_t* gsc, size_t len, const gsc_index* ix, int 
     if (!gsc || !ix || !pcm || !pcm_len) return set_last_error("gsc_decode_indexed: invalid argument");
     if (len != ix->ix.len) return set_last_error("gsc_decode_indexed: the index was built from another stream");
     t_dtim = gsc_decode_timing{};
+    ensure_tables(ix, gsc);
     Part pt{gsc, &ix->ix, frame_begin, frame_end};
     clamp_range(ix->ix, &pt.b, &pt.e);
     return decode_parts({pt}, pcm, pcm_len, nullptr, &t_dtim);
@@ -425,6 +448,10 @@ int gsc_index_locate(const gsc_index* ix, long long sample, int* frame, long lon
 
 void gsc_stream_free(gsc_stream* st) {
     if (!st) return;
+    if (st->set) {
+        set_last_error("gsc_stream_free: the stream belongs to a stream set; free the set");
+        return;
+    }
     int cur = 0;
     const bool sw = hipGetDevice(&cur) == hipSuccess && cur != st->device;
     if (sw) (void)hipSetDevice(st->device);
@@ -509,6 +536,7 @@ static int stream_open(const uint8_t* gsc, size_t len, const uint8_t* table, siz
     if (require_device() != 0) return -1;
     DEC_TRY(hipGetDevice(&h->device));
     if (open_device(gsc, ix, table != nullptr, true, &h->slabs, &h->lds_bytes) != 0) return -1;
+    h->view(h->slabs, 0);
     t_dtim.h2d_ms = t_otim.upload_ms;
     t_dtim.h2d_bytes = h->slabs.h2d_bytes;
     t_dtim.frames = int(ix.frames.size());
@@ -533,6 +561,191 @@ gsc_stream* gsc_stream_open_with_table(const uint8_t* gsc, size_t len, const uin
     // a refused table frees the stream, and with it every slab it uploaded
     std::unique_ptr<gsc_stream> h(new gsc_stream());
     return stream_open(gsc, len, table, table_len, h.get()) == 0 ? h.release() : nullptr;
+}
+
+// The device half of gsc_stream_set_open: one set of slabs for every stream,
+// the tables expanded and every table's claims checked there.  The runtime
+// calls are counted where they are made; none of them depends on `count`.
+static int set_open_device(const uint8_t* const* gscs, int count, const SetLayout& lay, gsc_stream_set* set) {
+    gsc_set_open_timing& tim = t_stim;
+    const double t0 = now_ms();
+    if (require_device() != 0) return -1;
+    DEC_TRY(hipGetDevice(&set->device));
+    // The default stream.  A stream of the library's own was built and measured, non-blocking and
+    // ordinary: with either one resident, crop calls on the default stream returned all-zero ranges
+    // now and then; without one, never (DESIGN.md "Stream sets").  The open waits for this stream only.
+    hipStream_t hs = nullptr;
+    struct CountAllocs {  // every Dev::alloc of this thread until the function returns
+        explicit CountAllocs(int* n) { t_alloc_count = n; }
+        ~CountAllocs() { t_alloc_count = nullptr; }
+    } count_allocs(&tim.device_allocations);
+    const size_t nf = lay.frames.size();
+    // host staging: the streams' bytes and checkpoints back to back, as the slabs hold them
+    std::vector<uint8_t> bytes(size_t(lay.total.bytes));
+    std::vector<uint64_t> cps(size_t(lay.total.cps));
+    parallel_for(count, host_threads(), [&](int i) {
+        const Index& ix = set->members[i].idx.ix;
+        const SlabPos& at = lay.base[size_t(i)];
+        if (ix.len) std::memcpy(bytes.data() + at.bytes, gscs[i], ix.len);
+        if (!ix.cps.empty()) std::memcpy(cps.data() + at.cps, ix.cps.data(), ix.cps.size() * sizeof(uint64_t));
+    });
+    // what only the open's two kernels read: per frame the packed tables' place and the bit count, the status word
+    const size_t src_bytes = nf * sizeof(TableSrc), bits_bytes = nf * sizeof(uint64_t);
+    std::vector<unsigned char> aux(src_bytes + bits_bytes + sizeof(unsigned long long));
+    unsigned long long status = kVerifyOk;
+    if (nf) std::memcpy(aux.data(), lay.src.data(), src_bytes);
+    if (nf) std::memcpy(aux.data() + src_bytes, lay.bits.data(), bits_bytes);
+    std::memcpy(aux.data() + src_bytes + bits_bytes, &status, sizeof(status));
+    Slabs<ResFrame>& s = set->slabs;
+    Dev<unsigned char> d_aux;
+    Event e1, e2, e3;
+    // A failure below leaves work queued on hs that reads the staging vectors and d_aux: wait for
+    // that stream before they go.  Declared last, so it runs first.
+    struct SyncOnFailure {
+        hipStream_t s;
+        bool armed;
+        int* waits;
+        ~SyncOnFailure() {
+            if (!armed) return;
+            (void)hipStreamSynchronize(s);
+            ++*waits;
+        }
+    } on_failure{hs, true, &tim.synchronisations};
+    if (s.alloc(lay.total, nf) != 0) return -1;  // the five slabs
+    DEC_TRY(d_aux.alloc(aux.size()));
+    DEC_TRY(hipEventCreate(&e1.e));
+    DEC_TRY(hipEventCreate(&e2.e));
+    DEC_TRY(hipEventCreate(&e3.e));
+    if (copy_pieces(s.bytes.p, bytes.data(), bytes.size(), hs, &tim) != 0 ||
+        copy_pieces(s.cps.p, cps.data(), cps.size() * sizeof(uint64_t), hs, &tim) != 0 ||
+        copy_pieces(s.frames.p, lay.frames.data(), nf * sizeof(ResFrame), hs, &tim) != 0 ||
+        copy_pieces(d_aux.p, aux.data(), aux.size(), hs, &tim) != 0)
+        return -1;
+    const TableSrc* d_src = reinterpret_cast<const TableSrc*>(d_aux.p);
+    const uint64_t* d_bits = reinterpret_cast<const uint64_t*>(d_aux.p + src_bytes);
+    unsigned long long* d_status = reinterpret_cast<unsigned long long*>(d_aux.p + src_bytes + bits_bytes);
+    tim.upload_ms = now_ms() - t0;
+    DEC_TRY(hipEventRecord(e1.e, hs));
+    DEC_TRY(gsc_launch_expand_tables(s.frames.p, d_src, int(nf), lay.total.cb, s.bytes.p, s.nwords * 4, s.cb.p, s.ncb,
+                                     s.att.p, s.natt, hs, &tim.launches));
+    DEC_TRY(hipEventRecord(e2.e, hs));
+    // walked members' checkpoints pass trivially: one launch over everything
+    DEC_TRY(gsc_launch_decode_verify(s.frames.p, d_bits, int(nf), s.cps.p, s.ncp, s.words(), s.nwords, d_status, hs,
+                                     &tim.launches));
+    DEC_TRY(hipEventRecord(e3.e, hs));
+    DEC_TRY(hipMemcpyAsync(&status, d_status, sizeof(status), hipMemcpyDeviceToHost, hs));
+    on_failure.armed = false;  // the wait is made here
+    const hipError_t waited = hipStreamSynchronize(hs);  // the default stream, not the device
+    ++tim.synchronisations;
+    DEC_TRY(waited);
+    float ms_e = 0, ms_v = 0;
+    DEC_TRY(hipEventElapsedTime(&ms_e, e1.e, e2.e));
+    DEC_TRY(hipEventElapsedTime(&ms_v, e2.e, e3.e));
+    tim.expand_ms = ms_e;
+    tim.verify_ms = ms_v;
+    if (status != kVerifyOk) {
+        // the smallest failing checkpoint of the slab: the lowest failing stream's first
+        const int64_t c = int64_t(status >> 8);
+        const int si = set_stream_of_checkpoint(lay, c);
+        const unsigned long long local = (unsigned long long)(c - lay.base[size_t(si)].cps) << 8 | (status & 0xff);
+        return set_last_error("gsc stream set: stream " + std::to_string(si) + ": " +
+                              verify_message(set->members[si].idx.ix, local));
+    }
+    return 0;
+}
+
+gsc_stream_set* gsc_stream_set_open(const uint8_t* const* gscs, const size_t* lens, const uint8_t* const* tables,
+                                    const size_t* table_lens, int count) {
+    t_stim = gsc_set_open_timing{};
+    const double t0 = now_ms();
+    if (count <= 0 || !gscs || !lens || (tables && !table_lens)) {
+        set_last_error(count <= 0 ? "gsc_stream_set_open: no streams" : "gsc_stream_set_open: invalid argument");
+        return nullptr;
+    }
+    // a refused stream frees the set, and with it everything it allocated
+    std::unique_ptr<gsc_stream_set> set(new gsc_stream_set());
+    set->members.reset(new gsc_stream[size_t(count)]);
+    set->count = count;
+    std::vector<std::string> errs(static_cast<size_t>(count));
+    std::vector<char> failed(static_cast<size_t>(count), 0);
+    parallel_for(count, host_threads(), [&](int i) {
+        Index* ix = &set->members[i].idx.ix;
+        const uint8_t* t = tables ? tables[i] : nullptr;
+        const int rc = t ? index_from_table(gscs[i], lens[i], t, table_lens[i], ix, &errs[size_t(i)], nullptr, false)
+                         : decode_walk(gscs[i], lens[i], ix, &errs[size_t(i)]);
+        if (rc != 0) {
+            failed[size_t(i)] = 1;
+        } else if (!t) {
+            index_drop_tables(ix);  // the device expands every member's tables, the host on demand
+        }
+    });
+    std::vector<const Index*> ixs(static_cast<size_t>(count));
+    for (int i = 0; i < count; ++i) {
+        if (failed[size_t(i)]) {
+            set_last_error("gsc stream set: stream " + std::to_string(i) + ": " + errs[size_t(i)]);
+            return nullptr;
+        }
+        ixs[size_t(i)] = &set->members[i].idx.ix;
+    }
+    SetLayout lay;
+    std::string err;
+    if (set_layout(ixs.data(), count, &lay, &err) != 0) {
+        set_last_error(err);
+        return nullptr;
+    }
+    t_stim.host_ms = now_ms() - t0;
+    t_stim.streams = count;
+    t_stim.frames = (long long)lay.frames.size();
+    t_stim.checkpoints = lay.total.cps;
+    if (set_open_device(gscs, count, lay, set.get()) != 0) return nullptr;
+    for (int i = 0; i < count; ++i) {
+        gsc_stream& m = set->members[i];
+        m.device = set->device;
+        for (const IndexFrame& f : m.idx.ix.frames) m.lds_bytes = std::max(m.lds_bytes, frame_lds_bytes(f));
+        m.view(set->slabs, lay.frame0[size_t(i)]);
+        m.set = set.get();
+    }
+    t_stim.total_ms = now_ms() - t0;
+    return set.release();
+}
+
+int gsc_stream_set_count(const gsc_stream_set* set) { return set ? set->count : set_last_error("null stream set"); }
+
+gsc_stream* gsc_stream_set_stream(gsc_stream_set* set, int i) {
+    if (!set || i < 0 || i >= set->count) {
+        set_last_error(set ? "gsc_stream_set_stream: no stream " + std::to_string(i) : std::string("null stream set"));
+        return nullptr;
+    }
+    return &set->members[i];
+}
+
+void gsc_stream_set_free(gsc_stream_set* set) {
+    if (!set) return;
+    int cur = 0;
+    const bool sw = hipGetDevice(&cur) == hipSuccess && cur != set->device;
+    if (sw) (void)hipSetDevice(set->device);
+    (void)hipDeviceSynchronize();  // queued crop decodes still read the slabs
+    delete set;
+    if (sw) (void)hipSetDevice(cur);
+}
+
+void gsc_last_set_open_timing(gsc_set_open_timing* t) {
+    if (t) *t = t_stim;
+}
+
+int gsc_stream_tables(const gsc_stream* st, int frame, int16_t* cb_out, uint8_t* att_out) {
+    if (!st || !cb_out || !att_out) return set_last_error("gsc_stream_tables: invalid argument");
+    if (frame < 0 || size_t(frame) >= st->idx.ix.frames.size())
+        return set_last_error("gsc_stream_tables: no frame " + std::to_string(frame));
+    ResFrame r{};
+    DEC_TRY(hipMemcpy(&r, st->frames + frame, sizeof(r), hipMemcpyDeviceToHost));
+    const int64_t slots = (int64_t(r.count) * r.cs + 7) & ~int64_t(7);
+    if (r.count < 0 || r.cs < 0 || r.cb_off < 0 || r.cb_off + slots > st->ncb || r.att_off < 0 ||
+        r.att_off + r.count > st->natt)
+        return set_last_error("gsc_stream_tables: the frame's tables lie outside the slabs");
+    if (slots) DEC_TRY(hipMemcpy(cb_out, st->cb + r.cb_off, size_t(slots) * sizeof(int16_t), hipMemcpyDeviceToHost));
+    if (r.count) DEC_TRY(hipMemcpy(att_out, st->att + r.att_off, size_t(r.count), hipMemcpyDeviceToHost));
+    return 0;
 }
 
 gsc_index* gsc_index_create_with_table(const uint8_t* gsc, size_t len, const uint8_t* table, size_t table_len) {
@@ -640,10 +853,9 @@ int gsc_decode_crops(gsc_stream* const* streams, int nstreams, const gsc_crop* c
     for (size_t i = 0; i < njob; ++i) {
         const PlanCrop& pc = plan.crops[i];
         const gsc_stream& st = *streams[pc.stream];
-        const Slabs<ResFrame>& sl = st.slabs;
-        hj[i] = CropJob{sl.frames.p, sl.cps.p, sl.words(), sl.cb.p,  sl.att.p, sl.ncp, sl.nwords, sl.ncb,
-                        sl.natt,     pc.begin, pc.count,   int32_t(st.idx.ix.frames.size()),
-                        pc.f0,       pc.f1,    pc.piece0};
+        hj[i] = CropJob{st.frames, st.cps,   st.words, st.cb,    st.att, st.ncp, st.nwords, st.ncb,
+                        st.natt,   pc.begin, pc.count, int32_t(st.idx.ix.frames.size()),
+                        pc.f0,     pc.f1,    pc.piece0};
         lds_bytes = std::max(lds_bytes, st.lds_bytes);
     }
     if (npc) std::memcpy(host.data() + njob * sizeof(CropJob), plan.pieces.data(), npc * sizeof(CropPiece));

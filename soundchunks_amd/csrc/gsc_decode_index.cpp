@@ -246,7 +246,7 @@ void index_table_write(const Index& ix, std::vector<uint8_t>* out) {
 }
 
 int index_from_table(const uint8_t* g, size_t len, const uint8_t* table, size_t tlen, Index* ix, std::string* err,
-                     const ParallelRunner* par) {
+                     const ParallelRunner* par, bool expand) {
     *ix = Index();
     if (!g || len == 0) {
         if (err) *err = "gsc decode: empty stream";
@@ -320,6 +320,10 @@ int index_from_table(const uint8_t* g, size_t len, const uint8_t* table, size_t 
     ix->len = len;
     ix->cps.resize(size_t(P));
     for (size_t i = 0; i < size_t(P); ++i) ix->cps[i] = rd64(tc + 8 * i);
+    if (!expand) {
+        ix->has_tables = false;
+        return 0;
+    }
     ix->att.resize(natt);
     ix->codebook.assign(ncb, 0);
     auto tables = [&](int k) {
@@ -331,6 +335,69 @@ int index_from_table(const uint8_t* g, size_t len, const uint8_t* table, size_t 
     } else {
         for (size_t k = 0; k < size_t(F); ++k) tables(int(k));
     }
+    return 0;
+}
+
+void index_expand_tables(const uint8_t* g, Index* ix) {
+    if (ix->has_tables) return;
+    size_t natt = 0, ncb = 0;
+    for (const IndexFrame& f : ix->frames) {
+        natt = std::max(natt, f.att_first + size_t(f.count));
+        ncb = std::max(ncb, f.cb_first + codebook_slots(f));
+    }
+    ix->att.assign(natt, 0);
+    ix->codebook.assign(ncb, 0);
+    for (const IndexFrame& f : ix->frames)
+        frame_tables_expand(g, f, ix->att.data() + f.att_first, ix->codebook.data() + f.cb_first);
+    ix->has_tables = true;
+}
+
+void index_drop_tables(Index* ix) {
+    std::vector<int16_t>().swap(ix->codebook);
+    std::vector<uint8_t>().swap(ix->att);
+    ix->has_tables = false;
+}
+
+int index_table_split(const uint8_t* g, size_t len, const uint8_t* table, size_t tlen, const size_t* part_bytes,
+                      int nparts, std::vector<std::vector<uint8_t>>* out, std::string* err) {
+    out->assign(size_t(std::max(nparts, 0)), std::vector<uint8_t>());
+    if (!g || !table || tlen < kTableHeaderBytes || std::memcmp(table, "GSCT", 4) != 0)
+        return table_fail(err, "shorter than its 32-byte header, or bad magic");
+    if (rd32(table + 4) != kTableVersion || rd32(table + 8) != uint32_t(kDecodeS))
+        return table_fail(err, "version " + std::to_string(rd32(table + 4)) + " with " + std::to_string(rd32(table + 8)) +
+                                   " symbols per checkpoint, this library writes version " +
+                                   std::to_string(kTableVersion) + " with " + std::to_string(kDecodeS));
+    const uint64_t F = rd32(table + 12), P = rd64(table + 24), body = uint64_t(tlen - kTableHeaderBytes);
+    if (16 * F > body || P > (body - 16 * F) / 8 || kTableHeaderBytes + 16 * F + 8 * P != uint64_t(tlen) ||
+        rd64(table + 16) != uint64_t(len))
+        return table_fail(err, "not the table of these " + std::to_string(len) + " bytes");
+    const uint8_t* tf = table + kTableHeaderBytes;
+    const uint8_t* tc = tf + 16 * F;
+    // the files of a batch may differ in ChannelCount and SampleRate: every frame is read on its own
+    uint64_t k = 0, cp = 0, start = 0;
+    for (int p = 0; p < nparts; ++p) {
+        const uint64_t end = start + uint64_t(part_bytes[p]);
+        if (end < start || end > uint64_t(len)) return table_fail(err, "the pieces are longer than the stream");
+        Index part;
+        for (; k < F && rd64(tf + 16 * k) < end; ++k) {
+            const uint64_t off = rd64(tf + 16 * k), next = k + 1 < F ? rd64(tf + 16 * (k + 1)) : uint64_t(len);
+            if (off < start || next > end || next < off) return table_fail(err, "a frame lies across two pieces");
+            IndexFrame f;
+            if (frame_head(g, len, size_t(off), size_t(k), nullptr, &f, err) != 0) return -1;
+            const uint64_t ncp = (uint64_t(f.nsym) + uint64_t(kDecodeS) - 1) / uint64_t(kDecodeS);
+            if (ncp > P - cp) return table_fail(err, "fewer checkpoints than the frames' symbols need");
+            IndexFrame q;
+            q.off = size_t(off - start);
+            q.nbits = rd64(tf + 16 * k + 8);
+            part.frames.push_back(q);
+            for (uint64_t i = 0; i < ncp; ++i) part.cps.push_back(rd64(tc + 8 * (cp + i)));
+            cp += ncp;
+        }
+        part.len = part_bytes[p];
+        if (!part.frames.empty()) index_table_write(part, &(*out)[size_t(p)]);
+        start = end;
+    }
+    if (start != uint64_t(len) || k != F || cp != P) return table_fail(err, "the pieces do not cover the stream");
     return 0;
 }
 

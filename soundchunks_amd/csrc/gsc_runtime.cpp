@@ -1693,6 +1693,45 @@ int gsc_encode_prepared_with_table(gsc_prepared* p, int frame_begin, int frame_e
     return 0;
 }
 
+int gsc_encode_prepared_files_with_tables(gsc_prepared* p, int frame_begin, int frame_end, uint8_t** out,
+                                          size_t* out_len, size_t* file_bytes, uint8_t** tables, size_t* tables_len,
+                                          size_t* table_bytes) {
+    if (!p || !out || !out_len || !file_bytes || !tables || !tables_len || !table_bytes)
+        return fail("gsc_encode_prepared_files_with_tables: null argument");
+    if (check_loaded(p, frame_begin, frame_end, "gsc_encode_prepared_files_with_tables") != 0) return -1;
+    t_tim = gsc_timing{};
+    std::vector<uint8_t> t;
+    if (encode_prepared(p->enc, frame_begin, frame_end, out, out_len, file_bytes, nullptr, &t) != 0) return -1;
+    t_tim.host_prepare_ms = 0;  // paid once, in gsc_prepare
+    // the range's table, cut at the files' byte counts and rebased to each file's first byte
+    const int nfiles = int(p->enc.file_first().size()) - 1;
+    std::vector<std::vector<uint8_t>> per;
+    std::string err;
+    size_t total = 0;
+    if (t.empty()) {
+        per.assign(size_t(nfiles), std::vector<uint8_t>());
+    } else if (index_table_split(*out, *out_len, t.data(), t.size(), file_bytes, nfiles, &per, &err) != 0) {
+        std::free(*out);
+        *out = nullptr;
+        return fail(err);
+    }
+    for (const auto& v : per) total += v.size();
+    *tables = static_cast<uint8_t*>(std::malloc(std::max<size_t>(total, 1)));
+    if (!*tables) {
+        std::free(*out);
+        *out = nullptr;
+        return fail("out of host memory");
+    }
+    size_t at = 0;
+    for (int f = 0; f < nfiles; ++f) {
+        if (!per[size_t(f)].empty()) std::memcpy(*tables + at, per[size_t(f)].data(), per[size_t(f)].size());
+        table_bytes[f] = per[size_t(f)].size();
+        at += per[size_t(f)].size();
+    }
+    *tables_len = total;
+    return 0;
+}
+
 double gsc_prepared_prepare_ms(const gsc_prepared* p) { return p ? p->prepare_ms : 0.0; }
 
 gsc_prepared* gsc_prepare_many(const uint8_t* const* wavs, const size_t* lens, int nfiles, const gsc_options* o) {

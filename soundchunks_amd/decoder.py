@@ -9,7 +9,9 @@ no CPU fallback for the decode itself; the index needs no GPU.
 ``Decoder.open(gsc)`` keeps a stream on the device (``ResidentStream``);
 ``Decoder.decode_crops`` then decodes batches of sample ranges of such streams
 straight into a torch tensor on the device, and ``decode_samples`` one range to
-numpy.  torch is imported by ``decode_crops`` alone.
+numpy.  ``Decoder.open_many(gscs, tables)`` opens a whole corpus as one
+``StreamSet`` at a fixed number of runtime calls.  torch is imported by
+``decode_crops`` alone.
 """
 from __future__ import annotations
 
@@ -31,6 +33,20 @@ def _take(lib, pcm, n: int) -> np.ndarray:
         return np.ctypeslib.as_array(pcm, shape=(n,)).copy() if n > 0 else np.zeros(0, np.int16)
     finally:
         lib.gsc_free(pcm)
+
+
+def _byte_arrays(seq):
+    """(uint8_t *[n], size_t[n], what keeps them alive) of a list of bytes-like objects; None entries
+    become NULL with length 0.  bytes objects are passed as they are, without a numpy view each."""
+    n = len(seq)
+    U8P = ctypes.POINTER(ctypes.c_uint8)
+    lens = (ctypes.c_size_t * max(1, n))(*[0 if b is None else len(b) for b in seq])
+    if all(b is None or isinstance(b, bytes) for b in seq):
+        arr = (ctypes.c_char_p * max(1, n))(*seq)
+        return ctypes.cast(arr, ctypes.POINTER(U8P)), lens, (arr, seq)
+    views = [None if b is None else _u8(b) for b in seq]
+    arr = (U8P * max(1, n))(*[U8P() if v is None else v[1] for v in views])
+    return arr, lens, views
 
 
 class Index:
@@ -115,14 +131,18 @@ class ResidentStream:
     uploaded once by ``Decoder.open``; sample ranges then decode without
     touching the bytes again (``decode_samples``, ``Decoder.decode_crops``)."""
 
-    def __init__(self, gsc: bytes, table: bytes | None = None):
+    def __init__(self, gsc: bytes, table: bytes | None = None, _member=None):
         lib = _lib.load()
-        arr, ptr = _u8(gsc)
-        if table is None:
-            h = lib.gsc_stream_open(ptr, len(arr))
+        self._set = None
+        if _member is not None:  # a StreamSet's view of one member: the handle is the set's
+            self._set, h = _member
         else:
-            tarr, tptr = _u8(table)
-            h = lib.gsc_stream_open_with_table(ptr, len(arr), tptr, len(tarr))
+            arr, ptr = _u8(gsc)
+            if table is None:
+                h = lib.gsc_stream_open(ptr, len(arr))
+            else:
+                tarr, tptr = _u8(table)
+                h = lib.gsc_stream_open_with_table(ptr, len(arr), tptr, len(tarr))
         if not h:
             raise _lib.GscError(lib.gsc_last_error().decode(errors="replace"))
         self._h = h
@@ -149,9 +169,82 @@ class ResidentStream:
         return self._h
 
     def close(self) -> None:
-        if getattr(self, "_h", None):
+        if getattr(self, "_set", None) is not None:
+            self._set.close()  # a member lives and ends with its set
+        elif getattr(self, "_h", None):
             self.index.close()
             _lib.load().gsc_stream_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            if getattr(self, "_set", None) is None:
+                self.close()
+        except Exception:
+            pass
+
+
+class StreamSet:
+    """Many ``.gsc`` streams opened as one resident set (``gsc_stream_set``):
+    one set of device slabs, tables expanded and seek tables checked on the
+    device, a fixed number of runtime calls whatever ``len(gscs)``.  ``ss[i]``
+    is a ``ResidentStream`` view of member i; ``ss.streams`` goes wherever a
+    list of resident streams goes, alone or mixed with others."""
+
+    def __init__(self, gscs, tables=None):
+        gscs = list(gscs)
+        tables = None if tables is None else list(tables)
+        if tables is not None and len(tables) != len(gscs):
+            raise _lib.GscError(f"open_many: {len(gscs)} streams, {len(tables)} tables")
+        for what, seq in (("stream", gscs), ("table", tables or [])):
+            for i, b in enumerate(seq):
+                if not isinstance(b, (bytes, bytearray, memoryview)) and not (what == "table" and b is None):
+                    raise _lib.GscError(f"open_many: {what} {i} is {type(b).__name__}, not bytes")
+        # the set keeps the streams for Index.decode, which builds the host tables from them on first
+        # use: they must stay the bytes the device holds, so anything mutable is copied now
+        gscs = [g if isinstance(g, bytes) else bytes(g) for g in gscs]
+        lib = _lib.load()
+        n = len(gscs)
+        ptrs, lens, _alive = _byte_arrays(gscs)  # the library copies what it keeps during the call
+        tptrs = tlens = None
+        if tables is not None:
+            tptrs, tlens, _alive_t = _byte_arrays(tables)
+        h = lib.gsc_stream_set_open(ptrs, lens, tptrs, tlens, n)
+        if not h:
+            raise _lib.GscError(lib.gsc_last_error().decode(errors="replace"))
+        self._h = h
+        self._gscs = gscs
+        self._streams = [None] * n  # views are made when asked for: an open costs no Python per stream
+
+    def __len__(self) -> int:
+        return len(self._streams)
+
+    def __getitem__(self, i):
+        if isinstance(i, slice):
+            return [self[j] for j in range(*i.indices(len(self)))]
+        i = range(len(self))[i]
+        if self._streams[i] is None:
+            if not getattr(self, "_h", None):
+                raise _lib.GscError("the resident stream is closed")
+            self._streams[i] = ResidentStream(self._gscs[i],
+                                              _member=(self, _lib.load().gsc_stream_set_stream(self._h, i)))
+        return self._streams[i]
+
+    @property
+    def streams(self):
+        return [self[i] for i in range(len(self))]
+
+    def decode_crops(self, crops, length: int, dtype=None, layout: str = "TC", out=None):
+        """``Decoder.decode_crops(self.streams, ...)``: crop stream indices count the set's members."""
+        return Decoder.decode_crops(self.streams, crops, length, dtype=dtype, layout=layout, out=out)
+
+    def close(self) -> None:
+        if getattr(self, "_h", None):
+            for s in self._streams:
+                if s is not None:
+                    s.index.close()
+                    s._h = None
+            _lib.load().gsc_stream_set_free(self._h)
             self._h = None
 
     def __del__(self):
@@ -184,6 +277,21 @@ class Decoder:
     @staticmethod
     def open(gsc: bytes, table: bytes | None = None) -> ResidentStream:
         return ResidentStream(gsc, table)
+
+    @staticmethod
+    def open_many(gscs, tables=None) -> StreamSet:
+        """Every stream of ``gscs`` as one resident set.  ``tables``: None (every
+        stream is walked on the host) or one entry per stream, a seek table or
+        None.  A stream that ``open`` would refuse fails the whole call; the
+        message names the lowest such stream."""
+        return StreamSet(gscs, tables)
+
+    @staticmethod
+    def last_set_open_timing() -> dict:
+        """Where the last ``open_many`` of this thread spent its time, and how many runtime calls it made."""
+        t = _lib.GscSetOpenTiming()
+        _lib.load().gsc_last_set_open_timing(ctypes.byref(t))
+        return {k: getattr(t, k) for k, _ in t._fields_}
 
     @staticmethod
     def last_open_timing() -> dict:

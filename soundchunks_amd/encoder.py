@@ -207,13 +207,32 @@ class Prepared:
         _lib.check(lib.gsc_prepared_file_frames(self._h, _ip(out)))
         return out
 
-    def encode_files(self, frame_begin: int = 0, frame_end: int = -1) -> tuple[bytes, list[int]]:
-        """Frames [frame_begin, frame_end) of the batch: (bytes, per-file byte counts)."""
+    def encode_files(self, frame_begin: int = 0, frame_end: int = -1, with_tables: bool = False):
+        """Frames [frame_begin, frame_end) of the batch: (bytes, per-file byte counts).
+        ``with_tables``: also every file's seek table, the table of that file's
+        returned bytes (empty for a file with no frame in the range), for
+        ``Decoder.open_many``: (bytes, per-file byte counts, [table per file])."""
         lib = _lib.load()
         n = lib.gsc_prepared_file_count(self._h)
         out = ctypes.POINTER(ctypes.c_uint8)()
         ln = ctypes.c_size_t(0)
         fb = (ctypes.c_size_t * max(1, n))()
+        if with_tables:
+            tabs = ctypes.POINTER(ctypes.c_uint8)()
+            tl = ctypes.c_size_t(0)
+            tb = (ctypes.c_size_t * max(1, n))()
+            _lib.check(lib.gsc_encode_prepared_files_with_tables(self._h, frame_begin, frame_end, ctypes.byref(out),
+                                                                 ctypes.byref(ln), fb, ctypes.byref(tabs),
+                                                                 ctypes.byref(tl), tb))
+            try:
+                blob, tables, o = ctypes.string_at(tabs, tl.value), [], 0
+                for i in range(n):
+                    tables.append(blob[o:o + int(tb[i])])
+                    o += int(tb[i])
+                return ctypes.string_at(out, ln.value), [int(fb[i]) for i in range(n)], tables
+            finally:
+                lib.gsc_free(out)
+                lib.gsc_free(tabs)
         _lib.check(lib.gsc_encode_prepared_files(self._h, frame_begin, frame_end, ctypes.byref(out), ctypes.byref(ln),
                                                  fb))
         try:
