@@ -49,7 +49,13 @@ struct ReduceFrame {
     int32_t loop_iters;   // out: batched-pipeline iterations (diagnostic); -1 = guard tripped
     int32_t tree_exact;   // out: passes whose kd-tree needed the sequential build (median ties)
     int32_t dcol;         // colCount = 2*ChunkSize (the residual's divisor, encoder.lpr:743); 0 = the slab width
-    uint64_t t_done;      // out: s_memrealtime (100 MHz) when the batched kernel finished the frame
+    // the batched scan's frame kind, written on the device before the scan
+    // (gsc_scan.hip scan_classify_kernel): 1 = K is the layout's 2^LOGK, dcol is
+    // the slab width and no centroid row is NaN -- the frame runs the PLAIN
+    // instantiation; 0 = the general one
+    int32_t plain;
+    int32_t plain_passes; // out: passes the PLAIN instantiation ran (diagnostic; the others: iters - plain_passes)
+    uint64_t t_done;     // out: s_memrealtime (100 MHz) when the batched kernel finished the frame
     // optional (batched kernel): when the frame is done, its final clusters are
     // copied to cl_host (host-mapped, N ints) and then *notify is set (system
     // scope), so the host post-processes it while other frames still scan

@@ -36,7 +36,12 @@ extern "C" hipError_t gsc_launch_scan_pass(int D, gsc::ReduceFrame* frames, int 
                                            int only_flagged, hipStream_t st);
 extern "C" hipError_t gsc_launch_scan_batch(int D, int logk, gsc::ReduceFrame* frames, int nframes, const float* X,
                                             float* C, int* is, const float* rate_tab, double tol, int max_passes,
-                                            int opts, float* tails, hipStream_t st);
+                                            int opts, float* tails, int kinds, hipStream_t st,
+                                            hipStream_t st_general, hipEvent_t fork, hipEvent_t join);
+extern "C" int gsc_scan_has_experiments(void);
+extern "C" int gsc_scan_has_plain(int D, int logk);
+extern "C" hipError_t gsc_launch_scan_classify(int D, int logk, gsc::ReduceFrame* frames, int nframes, const float* C,
+                                               hipStream_t st);
 extern "C" size_t gsc_scan_tail_floats_per_frame(int D, int logk);
 extern "C" hipError_t gsc_launch_atten(int cs, gsc::DspFrame* frames, int nframes, const double* samp, int64_t span,
                                        int ch, int obd, hipStream_t st);
@@ -247,6 +252,58 @@ int64_t tail_offset(int i) { return int64_t(i) * 4096 * 16; }
 // of the dominant kernel)
 std::atomic<int> g_scan_rounds{0};
 
+// The scan's experiment switches of the environment as the kernels' `opts`:
+// bit 0 (diagnostic GSC_SCAN_FULL_A1): full-dimension A1 bounds in every pass
+// bit 1 (GSC_SCAN_NO_PRUNE): no per-wave A1 pruning
+// bits 8..15 (GSC_SCAN_KB): queries per speculative batch (below the kernel's 32)
+// They exist only in a scan object built with -DGSC_SCAN_EXPERIMENTS
+// (tools/build_variant.sh); the product build says so once and ignores them.
+int scan_experiment_opts() {
+    const char* full = std::getenv("GSC_SCAN_FULL_A1");
+    const char* nopr = std::getenv("GSC_SCAN_NO_PRUNE");
+    const char* kb = std::getenv("GSC_SCAN_KB");
+    if (!full && !nopr && !kb) return 0;
+    if (!gsc_scan_has_experiments()) {
+        static std::atomic<bool> said{false};
+        if (!said.exchange(true))
+            std::fprintf(stderr,
+                         "soundchunks:%s%s%s set, but the scan experiments are not compiled into this build "
+                         "(tools/build_variant.sh NAME -DGSC_SCAN_EXPERIMENTS): ignored\n",
+                         full ? " GSC_SCAN_FULL_A1" : "", nopr ? " GSC_SCAN_NO_PRUNE" : "", kb ? " GSC_SCAN_KB" : "");
+        return 0;
+    }
+    return (full ? 1 : 0) | (nopr ? 2 : 0) | ((kb ? (std::atoi(kb) & 255) : 0) << 8);
+}
+
+// side stream and events of the batched scan, one set per device for the life
+// of the process: the general instantiation runs beside the PLAIN one
+// (gsc_scan.hip launch_scan).  `mu` serialises the enqueue of one round, so the
+// fork / join events of two host threads do not interleave.
+struct ScanFork {
+    hipStream_t side = nullptr;
+    hipEvent_t fork = nullptr, join = nullptr;
+    std::mutex mu;
+    hipError_t err = hipSuccess;
+    bool made = false;
+};
+
+ScanFork* scan_fork() {
+    constexpr int kMaxDev = 64;
+    static ScanFork forks[kMaxDev];
+    static std::mutex mu;
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDev) return nullptr;
+    std::lock_guard<std::mutex> lk(mu);
+    ScanFork& f = forks[dev];
+    if (!f.made) {
+        f.made = true;
+        f.err = hipStreamCreateWithFlags(&f.side, hipStreamNonBlocking);
+        if (f.err == hipSuccess) f.err = hipEventCreateWithFlags(&f.fork, hipEventDisableTiming);
+        if (f.err == hipSuccess) f.err = hipEventCreateWithFlags(&f.join, hipEventDisableTiming);
+    }
+    return f.err == hipSuccess ? &f : nullptr;
+}
+
 // all KNNScanReduce passes of a batch; converged frames exit early, the
 // generic launch after a batched one only runs the frames the batched kernel
 // handed over (NaN centroids)
@@ -261,6 +318,19 @@ hipError_t launch_scan_passes(int D, ReduceFrame* dfr, int nf, int K, const floa
         const hipError_t e = tails.alloc(size_t(tail_offset(nf)));
         if (e != hipSuccess) return e;
     }
+    // frame kinds to enqueue: no frame of this call is plain when K is not the
+    // layout's power of two (a host fact); whether a row is NaN is not one, so
+    // the general instantiation is always enqueued, on a stream of its own
+    // (K: the largest of the call's frames; the split layout has no PLAIN object)
+    const int kinds = batched && K == (1 << logk) && gsc_scan_has_plain(D, logk) ? 3 : 2;
+    ScanFork* sf = kinds == 3 ? scan_fork() : nullptr;
+    if (kinds == 3) {
+        if (!sf) return hipErrorUnknown;
+        // the frames' kind, once: it cannot change during the frame (descriptors start as general)
+        const hipError_t e = gsc_launch_scan_classify(D, logk, dfr, nf, C, nullptr);
+        if (e != hipSuccess) return e;
+    }
+    const int opts = batched ? scan_experiment_opts() : 0;
     int max_passes = kMaxScanIters;
     if (const char* e = std::getenv("GSC_SCAN_MAX_PASSES")) max_passes = std::max(1, std::min(kMaxScanIters, std::atoi(e)));
     // every launch advances each live frame by at least one pass (the batched
@@ -270,13 +340,15 @@ hipError_t launch_scan_passes(int D, ReduceFrame* dfr, int nf, int K, const floa
     static_assert(offsetof(ReduceFrame, generic) == offsetof(ReduceFrame, done) + sizeof(int32_t), "adjacent flags");
     for (int round = 0; round < max_passes; ++round) {
         if (batched) {
-            // opts bit 0 (diagnostic GSC_SCAN_FULL_A1): full-dimension A1 bounds in every pass
-            // bit 1 (GSC_SCAN_NO_PRUNE, experiment): no per-wave A1 pruning
-            // bits 8..15 (GSC_SCAN_KB, experiment): queries per speculative batch (below the kernel's 32)
-            const int opts = (std::getenv("GSC_SCAN_FULL_A1") ? 1 : 0) | (std::getenv("GSC_SCAN_NO_PRUNE") ? 2 : 0) |
-                             ((std::getenv("GSC_SCAN_KB") ? (std::atoi(std::getenv("GSC_SCAN_KB")) & 255) : 0) << 8);
-            hipError_t e =
-                gsc_launch_scan_batch(D, logk, dfr, nf, X, C, is, rate, tol, max_passes, opts, tails.p, nullptr);
+            hipError_t e;
+            if (sf) {
+                std::lock_guard<std::mutex> lk(sf->mu);
+                e = gsc_launch_scan_batch(D, logk, dfr, nf, X, C, is, rate, tol, max_passes, opts, tails.p, kinds, nullptr,
+                                          sf->side, sf->fork, sf->join);
+            } else {
+                e = gsc_launch_scan_batch(D, logk, dfr, nf, X, C, is, rate, tol, max_passes, opts, tails.p, kinds, nullptr,
+                                          nullptr, nullptr, nullptr);
+            }
             if (e != hipSuccess) return e;
             // the generic kernel runs only when the batched one handed a frame
             // over (an empty launch of it still costs ~30 ms: 256 large-LDS
@@ -406,8 +478,10 @@ int run_reduce_batch_dev(int D, int K, int precision, const std::vector<int>& Ns
         for (int i = 0; i < nf; ++i)
             if (fr[i].t_done) t0 = std::min<uint64_t>(t0, fr[i].t_done);
         for (int i = 0; i < nf; ++i)
-            std::fprintf(stderr, "frame %d: N %d passes %d slow %d restarts %d done +%.1f ms\n", i, fr[i].N, fr[i].iters,
-                         fr[i].slow, fr[i].restarts, fr[i].t_done ? double(fr[i].t_done - t0) / 1e5 : -1.0);
+            std::fprintf(stderr, "frame %d: N %d passes %d slow %d restarts %d done +%.1f ms kind %s plain_passes %d\n", i,
+                         fr[i].N, fr[i].iters, fr[i].slow, fr[i].restarts,
+                         fr[i].t_done ? double(fr[i].t_done - t0) / 1e5 : -1.0, fr[i].plain ? "plain" : "general",
+                         fr[i].plain_passes);
     }
     if (std::getenv("GSC_HOST_TIMING") && nf > 0 && fr[0].ystamps[6] + fr[0].ystamps[1] + fr[0].ystamps[2] != 0) {
         // stamps builds: yakmo phase clocks, mean over frames (cycles per pick)
@@ -1961,8 +2035,10 @@ int gsc_scan_reduce(int n, int d0, const float* x, int k, float* centroids, int*
     if (fr[0].loop_iters < 0) return fail("KNNScanReduce: batched pipeline made no progress (guard tripped)");
     if (std::getenv("GSC_SCAN_DEBUG"))
     {
-        std::fprintf(stderr, "scan: passes %d slow %d restarts %d loop_iters(last pass) %d err %.9g tree_exact %d\n",
-                     fr[0].iters, fr[0].slow, fr[0].restarts, fr[0].loop_iters, fr[0].err, fr[0].tree_exact);
+        std::fprintf(stderr, "scan: passes %d slow %d restarts %d loop_iters(last pass) %d err %.9g tree_exact %d"
+                             " kind %s plain_passes %d\n",
+                     fr[0].iters, fr[0].slow, fr[0].restarts, fr[0].loop_iters, fr[0].err, fr[0].tree_exact,
+                     fr[0].plain ? "plain" : "general", fr[0].plain_passes);
         std::fprintf(stderr, "stamps [prep A1 A2 B2 part3 part4 B1 vcheck won setup soloA soloDFS a2win a2far a2box a2out]");
         for (int w = 0; w < 8; ++w) {
             std::fprintf(stderr, "\n  w%d:", w);
@@ -1995,6 +2071,77 @@ int gsc_scan_reduce(int n, int d0, const float* x, int k, float* centroids, int*
         std::fprintf(stderr, "\nin-batch DFS answers %llu, of them failing at commit %llu", (unsigned long long)x2[8],
                      (unsigned long long)x2[9]);
         std::fprintf(stderr, "\n");
+    }
+    return 0;
+}
+
+// Internal (tests and tools; not part of include/soundchunks.h): KNNScanReduce
+// of several frames in ONE launch, from the caller's centroids, with a K per
+// frame.  x / centroids / clusters are the frames' arrays one after another
+// (ns[i] x d0, ks[i] x d0, ns[i]).  Out per frame: passes, the frame's kind
+// (1 = plain), the passes its PLAIN kernel ran, the last pass's residual.
+extern "C" int gsc_scan_reduce_frames(int nf, int d0, const int* ns, const float* x, const int* ks, float* centroids,
+                                      int* clusters, int precision, int* iters, int* plain, int* plain_passes,
+                                      double* err) {
+    if (ensure_device() != 0) return -1;
+    if (nf <= 0 || !ns || !ks || !x || !centroids || !clusters) return fail("gsc_scan_reduce_frames: invalid argument");
+    if (d0 <= 0 || d0 > 32) return fail("KNNScanReduce kernels support 1 <= d <= 32 features");
+    const int d = feature_stride((d0 + 1) / 2);
+    int kmax = 0, nmax = 0;
+    int64_t nsum = 0, ksum = 0;
+    for (int i = 0; i < nf; ++i) {
+        if (ns[i] <= 0 || ks[i] < 2 || ks[i] > kMaxK) return fail("gsc_scan_reduce_frames: invalid frame shape");
+        kmax = std::max(kmax, ks[i]);
+        nmax = std::max(nmax, ns[i]);
+        nsum += ns[i];
+        ksum += ks[i];
+    }
+    const int Kp = padded_k(kmax);
+    const std::vector<float> xp = pad_rows(x, int(nsum), d0, d);
+    std::vector<float> cp = pad_rows(centroids, int(ksum), d0, d);
+    std::vector<ReduceFrame> fr(static_cast<size_t>(nf));
+    int64_t no = 0, ko = 0;
+    for (int i = 0; i < nf; ++i) {
+        fr[i] = ReduceFrame{};
+        fr[i].x_off = no * d;
+        fr[i].c_off = ko * d;
+        fr[i].n_off = no;
+        fr[i].k_off = nsum + ko;
+        fr[i].ka_off = nsum + ksum + int64_t(i) * Kp;
+        fr[i].t_off = tail_offset(i);
+        fr[i].N = ns[i];
+        fr[i].K = ks[i];
+        fr[i].dcol = d0;
+        no += ns[i];
+        ko += ks[i];
+    }
+    DevBuf<float> dX, dC, dRate, dF;
+    DevBuf<int> dI;
+    DevBuf<ReduceFrame> dFr;
+    HIP_TRY(dF.alloc(size_t(nsum) * 4));
+    HIP_TRY(dX.alloc(xp.size()));
+    HIP_TRY(dC.alloc(cp.size()));
+    HIP_TRY(dI.alloc(size_t(nsum) + size_t(ksum) + size_t(nf) * size_t(Kp)));
+    HIP_TRY(dFr.alloc(size_t(nf)));
+    const std::vector<float> rt = rate_table(nmax);
+    HIP_TRY(dRate.alloc(rt.size()));
+    HIP_TRY(hipMemcpy(dX.p, xp.data(), sizeof(float) * xp.size(), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(dC.p, cp.data(), sizeof(float) * cp.size(), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(dRate.p, rt.data(), sizeof(float) * rt.size(), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(dFr.p, fr.data(), sizeof(ReduceFrame) * size_t(nf), hipMemcpyHostToDevice));
+    HIP_TRY(launch_scan_passes(d, dFr.p, nf, kmax, dX.p, dC.p, dI.p, dF.p, dRate.p, precision));
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(cp.data(), dC.p, sizeof(float) * cp.size(), hipMemcpyDeviceToHost));
+    compact_rows(&cp, int(ksum), d, d0);
+    std::memcpy(centroids, cp.data(), sizeof(float) * size_t(ksum) * d0);
+    HIP_TRY(hipMemcpy(clusters, dI.p, sizeof(int) * size_t(nsum), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(fr.data(), dFr.p, sizeof(ReduceFrame) * size_t(nf), hipMemcpyDeviceToHost));
+    for (int i = 0; i < nf; ++i) {
+        if (fr[i].loop_iters < 0) return fail("KNNScanReduce: batched pipeline made no progress (guard tripped)");
+        if (iters) iters[i] = fr[i].iters;
+        if (plain) plain[i] = fr[i].plain;
+        if (plain_passes) plain_passes[i] = fr[i].plain_passes;
+        if (err) err[i] = fr[i].err;
     }
     return 0;
 }

@@ -162,10 +162,20 @@ __device__ __forceinline__ uint32_t rec_sib(const WaveRecT<SL>& r, int ls, int i
 
 // improvements of ANN's DFS kept per query for the in-batch DFS answers (valid
 // == 2 below): a DFS with more keeps its query uncertified (solo resolution)
+//
+// Experiment switches (measured and not kept) are compiled in only
+// with -DGSC_SCAN_EXPERIMENTS (tools/build_variant.sh variants): the runtime
+// switches GSC_SCAN_FULL_A1 / GSC_SCAN_NO_PRUNE / GSC_SCAN_KB (the kernels'
+// `opts` argument) and the compile-time GSC_BOX_SHRINK and GSC_MAX_IMP.  The
+// product kernels carry none of them.
+#if !defined(GSC_SCAN_EXPERIMENTS) && (defined(GSC_BOX_SHRINK) || defined(GSC_MAX_IMP))
+#error "GSC_BOX_SHRINK and GSC_MAX_IMP are experiment switches: add -DGSC_SCAN_EXPERIMENTS"
+#endif
 #ifndef GSC_MAX_IMP
 #define GSC_MAX_IMP 8
 #endif
 constexpr int kMaxImp = GSC_MAX_IMP;
+static_assert(kMaxImp >= 1 && kMaxImp <= 16, "QRecT::B holds the improvement distances: 16 entries");
 
 template <int D>
 struct QRecT {        // A2 output per query
@@ -652,7 +662,8 @@ __device__ __forceinline__ float fsum16(float v) {  // sum over each aligned 16-
 template <class C, bool APPROX>
 __device__ __forceinline__ void a2_group(Scan2Shared<C>& sh, int j0, int nq, const float (*qrows)[C::QD],
                                          QRecT<C::D>* recs, int wcol0, const int* jlist, int lane,
-                                         bool half = false, float twh = 0.0f, float te = 0.0f, bool nanpass = false
+                                         bool half = false, float twh = 0.0f, float te = 0.0f, bool nanpass = false,
+                                         bool nans = true  // the kernel can meet NaN-first queries (false: plain frames)
 #ifdef GSC_STAMPS
                                          , uint64_t* acc = nullptr, uint64_t* tl = nullptr, uint64_t* xc = nullptr
 #endif
@@ -888,7 +899,7 @@ __device__ __forceinline__ void a2_group(Scan2Shared<C>& sh, int j0, int nq, con
             R.m2 = m2lo;
             R.rate = sh.rate[cs];
             R.farmask = farmask;
-            R.pad_ = nanf >= 0 ? 1 : 0;  // NaN-first query: no move, no check, residual NaN
+            if (nans) R.pad_ = nanf >= 0 ? 1 : 0;  // NaN-first query: no move, no check, residual NaN
         }
     }
     ASTAMP(15)
@@ -909,10 +920,10 @@ struct VPState {
 
 template <class C>
 __device__ __forceinline__ void vp_begin(Scan2Shared<C>& sh, int qb, int off, int pn, int a1, int lane, int& lg_pos,
-                                         int lg_tag, VPState& st) {
+                                         int lg_tag, VPState& st, bool nans) {
     if (lg_pos >= 0 && lg_tag < a1) lg_pos = -1;  // committed before the batch's snapshot
     // a NaN-first query moves nothing: a key of its own, so it joins no chain and no log entry
-    st.cs = lane < pn ? (sh.qrec[qb][off + lane].pad_ ? -100 - lane : sh.qrec[qb][off + lane].cstar) : -2;
+    st.cs = lane < pn ? (nans && sh.qrec[qb][off + lane].pad_ ? -100 - lane : sh.qrec[qb][off + lane].cstar) : -2;
     sh.vmeta[lane].x = lg_pos;
     sh.vmeta[lane].y = 0;
     if (lane < C::KB) sh.vcs[lane] = st.cs;
@@ -944,7 +955,7 @@ __device__ __forceinline__ void vp_begin(Scan2Shared<C>& sh, int qb, int off, in
 
 template <class C>
 __device__ __forceinline__ void vp_end(Scan2Shared<C>& sh, int qb, int off, int pn, int lane, int lg_pos,
-                                       const VPState& st, bool half, int par) {
+                                       const VPState& st, bool half, int par, bool nans) {
     constexpr int D = C::D, KB = C::KB;
     const int j = lane;
     const bool act = j < pn;
@@ -974,7 +985,7 @@ __device__ __forceinline__ void vp_end(Scan2Shared<C>& sh, int qb, int off, int 
             for (int d = 0; d < D; ++d) oc[d] = o[d];
             // exact live distance to c* (its snapshot coordinates when unmoved;
             // the A1 values of the batch are bounds only)
-            const bool nanq = R.pad_ != 0;
+            const bool nanq = nans && R.pad_ != 0;
             const float gpj = nanq ? __builtin_nanf("") : seqdist<D>(qv, oc);
             const bool okc = nanq || (R.valid != 0 && (pred < 0 || gpj < R.m2));
             const float rate = R.rate;
@@ -1032,7 +1043,8 @@ __device__ __forceinline__ bool dfs_keeps(const QRecT<D>& R, float du, int vp, f
 // (LDS atomic), and the checks start once wave 0's update chain (vp_end) of
 // this iteration is published (vp_ready).
 template <class C>
-__device__ __forceinline__ void v_check_grab(Scan2Shared<C>& sh, int qb, int off, int pn, int lane, int par) {
+__device__ __forceinline__ void v_check_grab(Scan2Shared<C>& sh, int qb, int off, int pn, int lane, int par,
+                                             bool nans) {
     constexpr int D = C::D, KB = C::KB, QPL = 64 / KB, LOGK = C::LOGK;
     constexpr int VPT = 2 * QPL;  // versions per trip
     constexpr int NTRIP = (C::KVER + VPT - 1) / VPT;
@@ -1043,7 +1055,7 @@ __device__ __forceinline__ void v_check_grab(Scan2Shared<C>& sh, int qb, int off
     const int j = lane % KB, grp = lane / KB;
     const int jr = j < pn ? j : 0;
     const QRecT<D>& R = sh.qrec[qb][off + jr];
-    const bool act = j < pn && R.pad_ == 0;  // a NaN-first answer holds whatever moved
+    const bool act = j < pn && !(nans && R.pad_ != 0);  // a NaN-first answer holds whatever moved
     const bool dfsa = R.valid == 2;          // the snapshot DFS answer (dfs_keeps)
     const int cs = R.cstar;
     const uint32_t fm = R.farmask;
@@ -1457,14 +1469,14 @@ __device__ __forceinline__ void refresh(Scan2Shared<C>& sh, float (&creg)[C::SL]
 template <class C>
 __device__ __forceinline__ void fold_commits(Scan2Shared<C>& sh, float (&creg)[C::SL][C::DR], float (&cn)[C::SL],
                                              float& cnmax, int vwave, int lane, int qb, int off, int kc, int par,
-                                             float* __restrict__ trow = nullptr) {
+                                             bool nans, float* __restrict__ trow = nullptr) {
     constexpr int SL = C::SL, LS = C::LS, D = C::D, DR = C::DR;
     int pp = 0;
     bool mine = false;
     if (lane < kc) {
         const QRecT<D>& R = sh.qrec[qb][off + lane];
         pp = R.cstar;
-        mine = sh.nxt[par][lane] >= kc && R.pad_ == 0 && (pp >> (6 + LS)) == vwave;
+        mine = sh.nxt[par][lane] >= kc && !(nans && R.pad_ != 0) && (pp >> (6 + LS)) == vwave;
     }
     uint64_t m = __ballot(mine);
     if (!m) return;
@@ -1573,24 +1585,43 @@ __device__ __forceinline__ void write_cstar(Scan2Shared<C>& sh, const float (&cr
 
 // ---------------------------------------------------------------------------
 // The kernel: one workgroup per frame (blockIdx.x = frame).
+//
+// Two instantiations per shape, enqueued for the same frame array; a workgroup
+// returns at once when its frame is the other kind (ReduceFrame::plain, written
+// by scan_classify_kernel below):
+//   PLAIN    the frame has K = 2^LOGK finite centroids and the slab's own
+//            colCount.  No NaN rows (a NaN row stays NaN and a finite row stays
+//            finite for the whole frame), no padding or dead leaves, no
+//            NaN-first answers: none of that state or control flow is compiled
+//            into this object.
+//   general  everything: NaN passes, K below 2^LOGK (pad_tree), padded slabs.
 // ---------------------------------------------------------------------------
-template <class C>
+template <class C, bool PLAIN>
 __global__ __launch_bounds__(C::NT) void scan_batch_kernel(ReduceFrame* __restrict__ frames, int nframes,
                                                            const float* __restrict__ Xall, float* __restrict__ Call,
                                                            int* __restrict__ i_scratch,
                                                            const float* __restrict__ rate_tab, double tol,
-                                                           int max_passes, int opts,
+                                                           int max_passes,
+#ifdef GSC_SCAN_EXPERIMENTS
+                                                           int opts,
+#endif
                                                            float* __restrict__ Tall) {
     constexpr int D = C::D, K = C::K, SL = C::SL, LS = C::LS, NWL = C::NWL, KB = C::KB;
     constexpr int kErrWave = NWL > 1 ? 1 : 0;  // residual + cluster ids (wave 0 keeps the log)
     constexpr bool PRUNE = true;               // A1 pruning by wave boxes
+    constexpr bool NANS = !PLAIN;              // NaN-first answers can occur (QRecT::pad_)
     // uncertified queries of a batch resolved in the batch by the exact DFS on the
     // snapshot (see the fixups below); GSC_INBATCH_DFS_D: the widest D that does it
     constexpr bool kInBatchDfs = D <= GSC_INBATCH_DFS_D;
+#ifdef GSC_SCAN_EXPERIMENTS
     const bool no_half = (opts & 1) != 0;      // diagnostic: full-dimension A1 bounds in every pass
     const bool no_prune = (opts & 2) != 0;     // experiment: every wave evaluates every query (no mid-A1 barrier)
     // experiment (opts bits 8..15): queries per speculative batch below KB
     const int kbe = ((opts >> 8) & 255) > 0 && ((opts >> 8) & 255) < KB ? ((opts >> 8) & 255) : KB;
+#else
+    constexpr bool no_half = false, no_prune = false;
+    constexpr int kbe = KB;
+#endif
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     Scan2Shared<C>& sh = *reinterpret_cast<Scan2Shared<C>*>(smem);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -1599,17 +1630,17 @@ __global__ __launch_bounds__(C::NT) void scan_batch_kernel(ReduceFrame* __restri
     const int fi0 = blockIdx.x, fstep = nframes;
     for (int fi = fi0; fi < nframes; fi += fstep) {
     ReduceFrame* frp = frames + fi;
-    if (uniform_int(frp->done) || uniform_int(frp->generic)) continue;
+    if (uniform_int(frp->done) || uniform_int(frp->generic) || (uniform_int(frp->plain) != 0) != PLAIN) continue;
     const int N = uniform_int(frp->N);
     // colCount of the residual (encoder.lpr:743): 2*ChunkSize, below D when the slab pads the features
-    const int dcol_i = uniform_int(frp->dcol) > 0 ? uniform_int(frp->dcol) : D;
+    const int dcol_i = PLAIN ? D : (uniform_int(frp->dcol) > 0 ? uniform_int(frp->dcol) : D);
     // best / colCount: a constant power-of-two divisor (an exact multiply) unless the slab is padded
-    auto per_col = [dcol_i](float v) { return dcol_i == D ? v / (float)D : v / (float)dcol_i; };
+    auto per_col = [=](float v) { return (PLAIN || dcol_i == D) ? v / (float)D : v / (float)dcol_i; };
     // ChunksPerFrame that is not a power of two (the -br cost loop,
     // encoder.lpr:1337-1351): ANN's tree over the Kr centroids, embedded in the
     // K = 2^LOGK leaf layout with padding leaves that are never visited (pad_tree)
-    const int Kr = uniform_int(frp->K);
-    const bool padded = Kr != K;
+    const int Kr = PLAIN ? K : uniform_int(frp->K);
+    const bool padded = !PLAIN && Kr != K;
     const float* __restrict__ X = Xall + uniform_i64(frp->x_off);
     float* C_ = Call + uniform_i64(frp->c_off);
     int* clusters = i_scratch + uniform_i64(frp->n_off);
@@ -1653,27 +1684,35 @@ __global__ __launch_bounds__(C::NT) void scan_batch_kernel(ReduceFrame* __restri
     // pass and finite rows stay finite (c + (x - c) * rate): their leaves carry
     // +inf distances here (inert in ANN's DFS once a real leaf was reached) and
     // the queries whose descent reaches one first take it (a2_group)
-    for (int w = tid; w < kMaxK / 32; w += nthreads) sh.nanid[w] = 0u;
-    __syncthreads();
-    int nan_rows = 0;
-    for (int k = tid; k < Kr; k += nthreads) {
-        bool nn = false;
+    int nan_rows = 0;  // plain frames have none (scan_classify_kernel)
+    if constexpr (!PLAIN) {
+        for (int w = tid; w < kMaxK / 32; w += nthreads) sh.nanid[w] = 0u;
+        __syncthreads();
+        for (int k = tid; k < Kr; k += nthreads) {
+            bool nn = false;
 #pragma unroll
-        for (int d = 0; d < D; ++d) nn |= C_[(int64_t)k * D + d] != C_[(int64_t)k * D + d];
-        if (nn) {
-            atomicOr(&sh.nanid[k >> 5], 1u << (k & 31));
-            nan_rows = 1;
+            for (int d = 0; d < D; ++d) nn |= C_[(int64_t)k * D + d] != C_[(int64_t)k * D + d];
+            if (nn) {
+                atomicOr(&sh.nanid[k >> 5], 1u << (k & 31));
+                nan_rows = 1;
+            }
         }
+        nan_rows = __syncthreads_or(nan_rows);
+    } else {
+        __syncthreads();  // sh.any_nan above; the previous pass's readers of the tree are done
     }
-    nan_rows = __syncthreads_or(nan_rows);
     if (padded) {
-        build_tree<D>(sh.t, sh.dist, C_, Kr);  // ANN's n/2 splits over the real centroids
-        pad_tree<C::LOGK>(sh.t, reinterpret_cast<int*>(sh.dist), Kr, tid, nthreads);
+        if constexpr (!PLAIN) {
+            build_tree<D>(sh.t, sh.dist, C_, Kr);  // ANN's n/2 splits over the real centroids
+            pad_tree<C::LOGK>(sh.t, reinterpret_cast<int*>(sh.dist), Kr, tid, nthreads);
+        }
     } else if (nan_rows) {  // NaN coordinates: annMaxSpread's and quickselect's exact order
-        if constexpr (K / nthreads >= 4)
-            build_tree_nan<D, C::LOGK, nthreads>(sh.t, sh.dist, sh.dfs_inc, C_);
-        else
-            build_tree<D>(sh.t, sh.dist, C_, K);
+        if constexpr (!PLAIN) {
+            if constexpr (K / nthreads >= 4)
+                build_tree_nan<D, C::LOGK, nthreads>(sh.t, sh.dist, sh.dfs_inc, C_);
+            else
+                build_tree<D>(sh.t, sh.dist, C_, K);
+        }
     } else if constexpr (K / nthreads < 4) {
         build_tree<D>(sh.t, sh.dist, C_, K);  // one or two leaves per thread: the sequential build
     } else if (!build_tree_fast<D, C::LOGK, nthreads>(sh.t, sh.dist, sh.dfs_inc, C_, &sh.slow_pos)) {
@@ -1701,15 +1740,23 @@ __global__ __launch_bounds__(C::NT) void scan_batch_kernel(ReduceFrame* __restri
         // its high child first and never enters the low one (box' = NaN), so
         // the leaves below a low child of such a node are dead for the pass
         bool dead = false;
-        if (nan_rows && p < K) {
+        if constexpr (!PLAIN) {
+            if (nan_rows && p < K) {
 #pragma unroll 1
-            for (int l = 0, h = 0; l < C::LOGK; ++l) {
-                const int bit = (p >> (C::LOGK - 1 - l)) & 1;
-                dead |= bit == 0 && sh.t.cv[h] != sh.t.cv[h];
-                h = 2 * h + 1 + bit;
+                for (int l = 0, h = 0; l < C::LOGK; ++l) {
+                    const int bit = (p >> (C::LOGK - 1 - l)) & 1;
+                    dead |= bit == 0 && sh.t.cv[h] != sh.t.cv[h];
+                    h = 2 * h + 1 + bit;
+                }
             }
         }
-        if (id != 0xFFFF && !dead && !((sh.nanid[id >> 5] >> (id & 31)) & 1u)) {
+        // a plain frame's leaves are all live (every dispatched shape fills its lanes: C::FULL)
+        bool live = true;
+        if constexpr (!PLAIN)
+            live = id != 0xFFFF && !dead && !((sh.nanid[id >> 5] >> (id & 31)) & 1u);
+        else if constexpr (!C::FULL)
+            live = id != 0xFFFF;
+        if (live) {
 #pragma unroll
             for (int d = 0; d < C::DR; ++d) {
                 creg[s][d] = C_[(int64_t)id * D + d];
@@ -1914,7 +1961,7 @@ __global__ __launch_bounds__(C::NT) void scan_batch_kernel(ReduceFrame* __restri
 #ifdef GSC_STAMPS_PREP
         STAMP(14)  // diagnostic split of "prep": loop top (into a2box's slot) vs the update chain
 #endif
-        if (wave == 0 && has_p) vp_begin<C>(sh, P_buf, P_off, P_n, vq_a10, ln, lg_pos, lg_tag, vst);
+        if (wave == 0 && has_p) vp_begin<C>(sh, P_buf, P_off, P_n, vq_a10, ln, lg_pos, lg_tag, vst, NANS);
         // The update chain right after its prep, so the V check can start
         // as soon as a wave is done with A1 (wave 0 reaches the mid-A1 barrier
         // early).  C5 -cs4 scan -3.2 % (5551 vs 5732 ms at 128 s) and no VGPR
@@ -1924,7 +1971,7 @@ __global__ __launch_bounds__(C::NT) void scan_batch_kernel(ReduceFrame* __restri
         constexpr bool kVpEarly = D <= GSC_VP_EARLY_D;
         if constexpr (kVpEarly) {
             if (wave == 0 && has_p) {
-                vp_end<C>(sh, P_buf, P_off, P_n, ln, lg_pos, vst, half, it & 1);
+                vp_end<C>(sh, P_buf, P_off, P_n, ln, lg_pos, vst, half, it & 1, NANS);
                 wave_lds_sync();
                 if (ln == 0) __hip_atomic_store(&sh.vp_ready, it + 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
             }
@@ -2014,7 +2061,7 @@ __global__ __launch_bounds__(C::NT) void scan_batch_kernel(ReduceFrame* __restri
             a1_mask(curm);
         }
         if constexpr (!kVpEarly) {
-            if (wave == 0 && has_p) vp_end<C>(sh, P_buf, P_off, P_n, ln, lg_pos, vst, half, it & 1);
+            if (wave == 0 && has_p) vp_end<C>(sh, P_buf, P_off, P_n, ln, lg_pos, vst, half, it & 1, NANS);
         }
         {
             STAMP(7)  // slot 7 = the rest of A1 (+ vp_end); slot 1 = the V check below
@@ -2029,7 +2076,7 @@ __global__ __launch_bounds__(C::NT) void scan_batch_kernel(ReduceFrame* __restri
                     while (__hip_atomic_load(&sh.vp_ready, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) != it + 1)
                         __builtin_amdgcn_s_sleep(1);
                 }
-                v_check_grab<C>(sh, P_buf, P_off, P_n, ln, it & 1);
+                v_check_grab<C>(sh, P_buf, P_off, P_n, ln, it & 1, NANS);
             }
         }
 #ifdef GSC_STAMPS
@@ -2133,7 +2180,7 @@ __global__ __launch_bounds__(C::NT) void scan_batch_kernel(ReduceFrame* __restri
 #pragma unroll 1
             for (int j0 = wave * 4; j0 < A_n; j0 += 4 * NWL)
                 a2_group<C, true>(sh, j0, A_n, sh.q[A_buf], sh.qrec[A_buf], 0, nullptr, ln, half, twh, te,
-                                  nan_rows != 0
+                                  NANS && nan_rows != 0, NANS
 #ifdef GSC_STAMPS
                                   , acc, &tlast, xc
 #endif
@@ -2173,7 +2220,7 @@ __global__ __launch_bounds__(C::NT) void scan_batch_kernel(ReduceFrame* __restri
                 write_cstar<C>(sh, creg, sh.qrec[A_buf], fx, 0, wave, ln, trow);
 #pragma unroll 1
                 for (int j0 = wave * 4; j0 < nfx; j0 += 4 * NWL)
-                    a2_group<C, false>(sh, j0, nfx, sh.q[A_buf], sh.qrec[A_buf], 0, sh.fxl, ln);
+                    a2_group<C, false>(sh, j0, nfx, sh.q[A_buf], sh.qrec[A_buf], 0, sh.fxl, ln, false, 0.0f, 0.0f, false, NANS);
                 lds_barrier();
                 // Queries the exact certificate cannot decide either: ANN's stale-tree
                 // DFS does not provably reach the snapshot's minimum (and mostly does
@@ -2201,7 +2248,7 @@ __global__ __launch_bounds__(C::NT) void scan_batch_kernel(ReduceFrame* __restri
                         float key;
                         // NaN passes: NaN and dead leaves are +inf in sh.dist, inert as in the
                         // solo resolution; NaN-first queries are certified (a2_group)
-                        if (nan_rows)
+                        if (NANS && nan_rows)
                             dfs_parallel_nan<C>(sh, sh.q[A_buf][jj], tid, ln, wave, bpos, key, &R);
                         else
                             dfs_parallel_call<C>(sh, sh.q[A_buf][jj], tid, ln, wave, bpos, key, &R);
@@ -2239,7 +2286,7 @@ __global__ __launch_bounds__(C::NT) void scan_batch_kernel(ReduceFrame* __restri
         }
         // every wave folds the committed updates of the centroids it owns, straight
         // from the update chain's rows (no barrier after the commit decision)
-        if (kc > 0) fold_commits<C>(sh, creg, cn, cnmax, vwave, ln, P_buf, P_off, kc, it & 1, trow);
+        if (kc > 0) fold_commits<C>(sh, creg, cn, cnmax, vwave, ln, P_buf, P_off, kc, it & 1, NANS, trow);
 #ifdef GSC_BOX_SHRINK
         // experiment: the pruning boxes only grow within a pass (every fold widens
         // them); re-fit them to the registers every GSC_BOX_SHRINK iterations (the
@@ -2273,7 +2320,7 @@ __global__ __launch_bounds__(C::NT) void scan_batch_kernel(ReduceFrame* __restri
             const QRecT<D>& R = sh.qrec[P_buf][P_off + (cj ? j : 0)];
             // the last committed update of each centroid becomes its log entry:
             // the entry already holding that centroid, else the r-th free entry
-            const bool lastc = cj && sh.nxt[it & 1][j] >= kc && R.pad_ == 0;
+            const bool lastc = cj && sh.nxt[it & 1][j] >= kc && !(NANS && R.pad_ != 0);
             int tgt = lastc ? sh.ient[j] : -1;
             const uint64_t need = __ballot(lastc && tgt < 0);
             const uint64_t freem = __ballot(lg_pos < 0);
@@ -2311,7 +2358,7 @@ __global__ __launch_bounds__(C::NT) void scan_batch_kernel(ReduceFrame* __restri
                 lds_barrier();
                 if (wave == 0)
                     a2_group<C, false>(sh, 0, 1, reinterpret_cast<const float(*)[C::QD]>(sh.qslow), &sh.qsolo, KB,
-                                       nullptr, ln);
+                                       nullptr, ln, false, 0.0f, 0.0f, false, NANS);
                 lds_barrier();
             }
             int bpos;
@@ -2325,7 +2372,7 @@ __global__ __launch_bounds__(C::NT) void scan_batch_kernel(ReduceFrame* __restri
                 // the centroid registers stay live across the DFS (it needs ~40 more
                 // VGPRs; parking the 128 in C and reloading them cost 2x the DFS time)
                 lds_barrier();  // sh.dist complete
-                if (nan_rows) {
+                if (NANS && nan_rows) {
                     // NaN leaves carry +inf here: inert, as the query's descent
                     // reaches a real leaf first (NaN-first queries never fail)
                     dfs_parallel_nan<C>(sh, sh.qslow, tid, ln, wave, bpos, key, nullptr);
@@ -2454,6 +2501,7 @@ __global__ __launch_bounds__(C::NT) void scan_batch_kernel(ReduceFrame* __restri
     prev_err = err;
     if (tid == 0) {
         frp->iters = pass + 1;
+        if constexpr (PLAIN) frp->plain_passes += 1;
         frp->slow += slow_total;
         frp->restarts += restarts;
         frp->err = err;
@@ -2481,22 +2529,97 @@ __global__ __launch_bounds__(C::NT) void scan_batch_kernel(ReduceFrame* __restri
     }
 }
 
+// The frame kind (ReduceFrame::plain), one workgroup per frame, once ahead of a
+// scan's first batched launch (gsc_launch_scan_classify): whether a centroid row is NaN is known only on the device
+// (yakmo's 0/0 means, or the caller's own centroids), and stays what it is for
+// the whole frame.  K and dcol are checked here too, so every caller of the
+// scan gets the same routing.
+__global__ __launch_bounds__(256) void scan_classify_kernel(ReduceFrame* __restrict__ frames, int nframes,
+                                                            const float* __restrict__ Call, int D, int K2) {
+    const int fi = blockIdx.x;
+    if (fi >= nframes) return;
+    ReduceFrame* frp = frames + fi;
+    if (uniform_int(frp->done)) return;
+    const int Kr = uniform_int(frp->K), dcol = uniform_int(frp->dcol);
+    const float* __restrict__ C_ = Call + uniform_i64(frp->c_off);
+    int nan = 0;
+    if (Kr == K2 && (dcol == 0 || dcol == D)) {
+        const int64_t n = (int64_t)Kr * D;
+        for (int64_t i = threadIdx.x; i < n; i += blockDim.x) nan |= C_[i] != C_[i] ? 1 : 0;
+    } else {
+        nan = 1;  // not plain by shape: the rows need no look
+    }
+    nan = __syncthreads_or(nan);
+    if (threadIdx.x == 0) frp->plain = nan ? 0 : 1;
+}
+
 }  // namespace gsc
 
 using namespace gsc;
 
+// kinds: bit 0 = enqueue the PLAIN instantiation (on st), bit 1 = the general
+// one (on st_general when given and both are enqueued, so a mixed batch runs
+// its two kinds side by side; fork / join: events of the caller)
 template <class C>
 static hipError_t launch_scan(ReduceFrame* frames, int nframes, const float* X, float* Cc, int* is,
-                              const float* rate_tab, double tol, int max_passes, int opts, float* tails,
-                              hipStream_t st) {
+                              const float* rate_tab, double tol, int max_passes, int opts, float* tails, int kinds,
+                              hipStream_t st, hipStream_t st_general, hipEvent_t fork, hipEvent_t join) {
     const size_t shm = sizeof(Scan2Shared<C>);
     static_assert(sizeof(Scan2Shared<C>) <= 160 * 1024, "LDS budget (160 KB per CU)");
-    hipError_t e = hipFuncSetAttribute((const void*)scan_batch_kernel<C>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)shm);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(scan_batch_kernel<C>, dim3(nframes), dim3(C::NT), shm, st, frames, nframes, X, Cc, is, rate_tab,
-                       tol, max_passes, opts, tails);
+    hipError_t e;
+    if (C::SPLIT) kinds = 2;  // no PLAIN object (gsc_scan_has_plain)
+    const bool both = (kinds & 3) == 3 && st_general != nullptr;
+    auto launch = [&](auto kernel, hipStream_t s) -> hipError_t {
+        hipError_t le = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
+        if (le != hipSuccess) return le;
+#ifdef GSC_SCAN_EXPERIMENTS
+        hipLaunchKernelGGL(kernel, dim3(nframes), dim3(C::NT), shm, s, frames, nframes, X, Cc, is, rate_tab, tol,
+                           max_passes, opts, tails);
+#else
+        (void)opts;
+        hipLaunchKernelGGL(kernel, dim3(nframes), dim3(C::NT), shm, s, frames, nframes, X, Cc, is, rate_tab, tol,
+                           max_passes, tails);
+#endif
+        return hipGetLastError();
+    };
+    if (kinds & 2) {
+        if (both) {
+            if ((e = hipEventRecord(fork, st)) != hipSuccess) return e;
+            if ((e = hipStreamWaitEvent(st_general, fork, 0)) != hipSuccess) return e;
+        }
+        if ((e = launch(scan_batch_kernel<C, false>, both ? st_general : st)) != hipSuccess) return e;
+        if (both && (e = hipEventRecord(join, st_general)) != hipSuccess) return e;
+    }
+    if constexpr (!C::SPLIT) {
+        if (kinds & 1) {
+            if ((e = launch(scan_batch_kernel<C, true>, st)) != hipSuccess) return e;
+        }
+    }
+    if ((kinds & 2) && both) return hipStreamWaitEvent(st, join, 0);
+    return hipSuccess;
+}
+
+// The split layout (D = 32, K = 4096) has no PLAIN object: built, it spilled
+// 204 VGPRs against the general object's 121 and ran the C3 bench 10 % slower
+// (profiles/scan_plain), so its frames stay general and are not classified.
+extern "C" int gsc_scan_has_plain(int D, int logk) { return !(D == 32 && logk == 12); }
+
+// The frames' kind (ReduceFrame::plain), once per scan and ahead of its first
+// batched launch; descriptors start as general (plain = 0).
+extern "C" hipError_t gsc_launch_scan_classify(int D, int logk, ReduceFrame* frames, int nframes, const float* Cc,
+                                               hipStream_t st) {
+    hipLaunchKernelGGL(scan_classify_kernel, dim3(nframes), dim3(256), 0, st, frames, nframes, Cc, D,
+                       gsc_scan_has_plain(D, logk) ? (1 << logk) : -1);
     return hipGetLastError();
+}
+
+// 1 when the experiment switches of the kernels' `opts` are compiled in (-DGSC_SCAN_EXPERIMENTS)
+extern "C" int gsc_scan_has_experiments(void) {
+#ifdef GSC_SCAN_EXPERIMENTS
+    return 1;
+#else
+    return 0;
+#endif
 }
 
 // Batched KNNScanReduce for every frame (K <= 2^logk, 2^logk in 256..4096; a
@@ -2504,14 +2627,19 @@ static hipError_t launch_scan(ReduceFrame* frames, int nframes, const float* X, 
 // D = 32 with K = 4096 in the split layout): each frame runs its passes from
 // frp->iters until it converges, reaches max_passes or meets a NaN pass (left
 // to the generic kernel).  Returns hipErrorInvalidValue for shapes it does not
-// cover.
+// cover.  Each frame runs in the instantiation of its kind (scan_batch_kernel);
+// `kinds` says which of the two the caller needs enqueued (bit 0 PLAIN, bit 1
+// general): only what the host knows without a read-back may clear a bit (no
+// frame has K = 2^logk: general only); NaN rows are found on the device.
+// `opts`: the experiment switches, ignored unless gsc_scan_has_experiments().
 extern "C" hipError_t gsc_launch_scan_batch(int D, int logk, ReduceFrame* frames, int nframes, const float* X,
                                             float* Cc, int* is, const float* rate_tab, double tol, int max_passes,
-                                            int opts, float* tails, hipStream_t st) {
+                                            int opts, float* tails, int kinds, hipStream_t st, hipStream_t st_general,
+                                            hipEvent_t fork, hipEvent_t join) {
 #define SB(DV, LK, SLV)                                                                                           \
     if (D == DV && logk == LK)                                                                                    \
         return launch_scan<ScanCfg<DV, LK, SLV>>(frames, nframes, X, Cc, is, rate_tab, tol, max_passes, opts, tails, \
-                                                 st);
+                                                 kinds, st, st_general, fork, join);
     // K below 4096: fewer leaves per lane, so a frame keeps (up to) 8 waves --
     // the per-search work there is latency (A2 certificates, V checks and the
     // commit spread over the waves): K = 256 / 512 one leaf per lane (4 / 8
@@ -2524,7 +2652,7 @@ extern "C" hipError_t gsc_launch_scan_batch(int D, int logk, ReduceFrame* frames
     // too: 4294 vs 4309 ms at the C2 bench shape, not kept)
     if (D == 32 && logk == 12)
         return launch_scan<ScanCfg<32, 12, 8, 16>>(frames, nframes, X, Cc, is, rate_tab, tol, max_passes, opts, tails,
-                                                   st);
+                                                   kinds, st, st_general, fork, join);
 #undef SB
     return hipErrorInvalidValue;
 }

@@ -3,6 +3,8 @@
 #   tools/build_variant.sh NAME [-src FILE.hip] -DFLAG ...  ->  soundchunks_amd/lib/variants/NAME/libsoundchunks_amd.so
 # (select it with GSC_LIB=...; the in-tree build must be current; -src: another
 # scan source, e.g. the previous commit's, compiled against the current headers)
+# The scan's experiment switches need -DGSC_SCAN_EXPERIMENTS: the runtime ones (GSC_SCAN_FULL_A1,
+# GSC_SCAN_NO_PRUNE, GSC_SCAN_KB) and -DGSC_BOX_SHRINK=N / -DGSC_MAX_IMP=N; the product build has none.
 set -e
 cd "$(dirname "$0")/../soundchunks_amd/csrc"
 name=$1; shift

@@ -1,7 +1,11 @@
 #!/bin/bash
 # scan A/B: half-dimension A1 bounds (default) vs full-dimension (GSC_SCAN_FULL_A1=1), ABAB on C5 -cs4,
-# the c4d corpus and C2; scan ms and bit_exact per run
+# the c4d corpus and C2; scan ms and bit_exact per run.  The switch is an experiment: it exists only in a
+# scan object built with -DGSC_SCAN_EXPERIMENTS (the product build ignores it with a notice), so both legs
+# run the variant library:  tools/build_variant.sh exp -DGSC_SCAN_EXPERIMENTS
 cd "${GRAFT_REPO_ROOT:-/root/repo}"
+export GSC_LIB=${GSC_LIB:-soundchunks_amd/lib/variants/exp/libsoundchunks_amd.so}
+[ -f "$GSC_LIB" ] || { echo "build the variant first: tools/build_variant.sh exp -DGSC_SCAN_EXPERIMENTS"; exit 2; }
 mkdir -p gpurun_out
 for r in 1 2; do
   for v in half full; do
