@@ -1689,12 +1689,21 @@ __global__ __launch_bounds__(C::NT) void scan_batch_kernel(ReduceFrame* __restri
         for (int w = tid; w < kMaxK / 32; w += nthreads) sh.nanid[w] = 0u;
         __syncthreads();
         for (int k = tid; k < Kr; k += nthreads) {
-            bool nn = false;
+            bool nn = false, fin = false;
 #pragma unroll
-            for (int d = 0; d < D; ++d) nn |= C_[(int64_t)k * D + d] != C_[(int64_t)k * D + d];
+            for (int d = 0; d < D; ++d) {
+                const bool n = C_[(int64_t)k * D + d] != C_[(int64_t)k * D + d];
+                nn |= n;
+                fin |= !n && d < dcol_i;  // the slab's padding features are zeros in every row
+            }
             if (nn) {
                 atomicOr(&sh.nanid[k >> 5], 1u << (k & 31));
                 nan_rows = 1;
+                // a row with NaN in some coordinates only (a caller's centroids;
+                // yakmo's 0/0 means are whole rows): a query answered with it
+                // still moves its finite coordinates, which the NaN-first answers
+                // here do not -- the pass runs in the generic kernel (any_nan below)
+                if (fin) sh.any_nan = 1;
             }
         }
         nan_rows = __syncthreads_or(nan_rows);

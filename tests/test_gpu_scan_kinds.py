@@ -15,63 +15,19 @@ import os
 import re
 import subprocess
 import sys
-from pathlib import Path
 
 import numpy as np
 import pytest
 
+from scan_frames import ROOT, bits as _bits, run_child
+
 pytestmark = pytest.mark.gpu
-ROOT = Path(__file__).resolve().parents[1]
 PASSES = 3
 N, K_POW2, K_ODD = 3000, 512, 485
-
-# Launches of several frames through the library's internal multi-frame scan
-# entry (gsc_scan_reduce_frames: caller centroids, a K per frame, one launch),
-# then one single-frame scan through the C ABI with a NaN row.
-CHILD = """
-import ctypes, sys
-sys.path[:0] = [{root!r}, {tests!r}]
-import numpy as np
-import soundchunks_amd as sc
-lib = sc.load()
-FP, IP, DP = (ctypes.POINTER(t) for t in (ctypes.c_float, ctypes.c_int, ctypes.c_double))
-fn = lib.gsc_scan_reduce_frames
-fn.restype = ctypes.c_int
-fn.argtypes = [ctypes.c_int, ctypes.c_int, IP, FP, IP, FP, IP, ctypes.c_int, IP, IP, IP, DP]
-z = np.load({inp!r})
-out = {{}}
-for launch, names in {launches!r}.items():
-    xs = [z["x_" + n] for n in names]
-    cs = [z["c_" + n] for n in names]
-    ns = np.array([len(a) for a in xs], dtype=np.int32)
-    ks = np.array([len(a) for a in cs], dtype=np.int32)
-    x = np.ascontiguousarray(np.concatenate(xs), dtype=np.float32)
-    c = np.ascontiguousarray(np.concatenate(cs), dtype=np.float32)
-    cl = np.zeros(int(ns.sum()), dtype=np.int32)
-    it, pl, pp = (np.zeros(len(names), dtype=np.int32) for _ in range(3))
-    err = np.zeros(len(names), dtype=np.float64)
-    rc = fn(len(names), x.shape[1], ns.ctypes.data_as(IP), x.ctypes.data_as(FP), ks.ctypes.data_as(IP),
-            c.ctypes.data_as(FP), cl.ctypes.data_as(IP), 3, it.ctypes.data_as(IP), pl.ctypes.data_as(IP),
-            pp.ctypes.data_as(IP), err.ctypes.data_as(DP))
-    assert rc == 0, sc.last_error() if hasattr(sc, "last_error") else rc
-    co = np.cumsum(np.concatenate([[0], ks])); no = np.cumsum(np.concatenate([[0], ns]))
-    for i, n in enumerate(names):
-        out[launch + "/" + n + "/c"] = c[co[i]:co[i + 1]]
-        out[launch + "/" + n + "/cl"] = cl[no[i]:no[i + 1]]
-        out[launch + "/" + n + "/meta"] = np.array([it[i], pl[i], pp[i]])
-        out[launch + "/" + n + "/err"] = err[i]
-c, cl, n = sc.scan_reduce(z["x_nan"], z["c_nan"], precision=3)
-out["abi/nan/c"], out["abi/nan/cl"], out["abi/nan/meta"] = c, cl, np.array([n, -1, -1])
-np.savez({outp!r}, **out)
-"""
 
 # plain + NaN rows + K = 485 in one launch (both kernels work on one frame
 # array, side by side); then each kernel's empty-grid case
 LAUNCHES = {"mixed": ["plain", "nan", "odd"], "plain_only": ["plain", "plain2"], "general_only": ["nan", "odd"]}
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
 
 
 def _inputs(d):
@@ -90,14 +46,14 @@ def _inputs(d):
 
 
 def _run_child(tmp_path, d, extra_env):
+    """Launches of several frames through the library's internal multi-frame
+    scan entry (scan_frames.py: caller centroids, a K per frame, one launch),
+    then one single-frame scan through the C ABI with a NaN row."""
     frames = _inputs(d)
-    inp, outp = tmp_path / "in.npz", tmp_path / "out.npz"
-    np.savez(inp, **{"x_" + k: v[0] for k, v in frames.items()}, **{"c_" + k: v[1] for k, v in frames.items()})
-    code = CHILD.format(root=str(ROOT), tests=str(ROOT / "tests"), inp=str(inp), outp=str(outp), launches=LAUNCHES)
-    env = dict(os.environ, GSC_SCAN_MAX_PASSES=str(PASSES), GSC_SCAN_DEBUG="1", **extra_env)
-    r = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=150)
-    assert r.returncode == 0, r.stderr[-2000:]
-    return frames, np.load(outp), r.stderr
+    launches = [(launch, "frames", names) for launch, names in LAUNCHES.items()] + [("abi", "abi", ["nan"])]
+    env = dict(GSC_SCAN_MAX_PASSES=str(PASSES), GSC_SCAN_DEBUG="1", **extra_env)
+    got, err = run_child(tmp_path, frames, launches, env)
+    return frames, got, err
 
 
 _ORACLE = {}
