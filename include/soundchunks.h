@@ -301,6 +301,72 @@ int gsc_stream_decode_samples(gsc_stream *st, long long begin, long long count, 
  * value; any other argument only queries.  The output does not depend on it. */
 int gsc_decode_crops_variant(int variant);
 
+/* ---- crops at a common sample rate and channel count -------------------------- */
+/* gsc_decode_crops with an output format: every row of the batch comes out at
+ * out_rate and with out_channels channels, whatever its stream's own.
+ * out_rate 0: no resampling, every stream keeps its rate; out_channels 0: the
+ * streams' count, which must then agree as in gsc_decode_crops.
+ *
+ * Units.  A crop's `begin` stays in source samples of its stream; `count` and
+ * `length` are output samples at out_rate.  With Fi the stream's rate, Fo =
+ * out_rate, g = gcd(Fi, Fo), L = Fo / g (the phases) and M = Fi / g, output n
+ * of a crop sits at source position (begin L + n M) / L: i0 its floor, phase
+ * p = (begin L + n M) mod L, in 64-bit integers.  The crop is clipped at the
+ * first n whose position is >= the stream's samples: written[i] = min(count,
+ * ceil((samples - begin) L / M)); the rest of the row is zero.  Source samples
+ * outside [0, samples) read as zero in the filter, those before `begin` are
+ * read from the stream: a crop is a slice of the resampled stream.
+ *
+ * Filter.  A windowed sinc under the exact Blackman window w(u) = 7938/18608 +
+ * 9240/18608 cos(pi u) + 1430/18608 cos(2 pi u) on |u| <= 1, 0 outside.  rho =
+ * min(1, Fo / Fi), Z = 16 zero crossings per side, W = Z / rho, T = ceil(W).
+ * Tap k in [-T + 1, T] of phase p has d = k - p / L and the ideal value h =
+ * rho sinc(rho d) w(d / W), sinc(x) = sin(pi x) / (pi x).  Per phase, in f64 on
+ * the host: c_k = round-half-even(2^24 h_k / sum_k h_k), then the remainder
+ * 2^24 - sum c_k is added to the tap of largest |h| (lowest k on a tie), so
+ * every phase sums to exactly 2^24 and a constant passes unchanged.  Per
+ * source channel acc = sum_k c_k x[i0 + k] in int64 and y = clamp((acc + 2^23)
+ * >> 24, -32768, 32767), an arithmetic shift; float32 output is y 2^-15.  A
+ * stream with Fi == Fo takes no filter: its int16 samples pass unchanged.
+ *
+ * Channels, applied to the int16 results y: equal counts copy; a mono stream
+ * is duplicated to every output channel; a mono output is m = floor((2 sum_k
+ * y_k + Cs) / (2 Cs)), floor toward -infinity (the mean, rounded half up).
+ * Any other pair of counts is refused, the stream and both counts named.
+ *
+ * Refused besides what gsc_decode_crops refuses, with nothing launched and
+ * both rates named: a rate <= 0, 2 T > 512 (Fo / Fi < 1/16), a table of more
+ * than 16 MiB (phases x taps x 4 bytes, e.g. 44101 -> 192000), and a filter
+ * whose 2 T + 2 samples times the stream's channels exceed the 24576 source
+ * samples a workgroup keeps.
+ *
+ * One launch: a workgroup takes gsc_resample_tile() output samples of a crop,
+ * decodes the source samples they read into LDS and filters from there.
+ * Stream order is gsc_decode_crops': no synchronisation, no sample copied to
+ * the host, with one exception: the first use of a pair of rates on a device
+ * builds its table on the host, uploads it with a blocking copy and keeps it
+ * for the life of the process.  The tables are never written again, so later
+ * calls on any stream use them unordered.  gsc_resample_prepare does that
+ * ahead of time. */
+typedef struct {
+    int dtype;         /* GSC_PCM_* */
+    int layout;        /* GSC_LAYOUT_* */
+    long long length;  /* output samples per row */
+    int out_rate;      /* Hz; 0: none */
+    int out_channels;  /* 0: the streams' */
+} gsc_crop_format;
+int gsc_decode_crops_fmt(gsc_stream *const *streams, int nstreams, const gsc_crop *crops, int ncrops,
+                         const gsc_crop_format *fmt, void *dst_device, void *hip_stream, long long *written);
+/* The table of a pair of rates: *phases rows of *taps int32, *coeff pointing
+ * into the process-wide cache (valid for the life of the process; do not
+ * free).  Host only, needs no device.  Equal rates give the one-phase table
+ * that gsc_decode_crops_fmt never applies. */
+int gsc_resample_table(int in_rate, int out_rate, int *phases, int *taps, const int32_t **coeff);
+/* the table of a pair on the calling thread's device, now instead of on first use */
+int gsc_resample_prepare(int in_rate, int out_rate);
+/* output samples of one workgroup of the resampling kernel */
+int gsc_resample_tile(void);
+
 /* ---- seek tables: opening a stream without the host walk -------------------- */
 /* A seek table is a side blob that holds what the walk finds by following the
  * stream's two chains: where every frame starts, how many bits its bitstream

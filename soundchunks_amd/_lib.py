@@ -117,6 +117,13 @@ class GscCrop(ctypes.Structure):
     _fields_ = [("stream", ctypes.c_int), ("begin", ctypes.c_longlong), ("count", ctypes.c_longlong)]
 
 
+class GscCropFormat(ctypes.Structure):
+    """Mirror of ``gsc_crop_format``: what ``gsc_decode_crops_fmt`` writes."""
+
+    _fields_ = [("dtype", ctypes.c_int), ("layout", ctypes.c_int), ("length", ctypes.c_longlong),
+                ("out_rate", ctypes.c_int), ("out_channels", ctypes.c_int)]
+
+
 PCM_INT16, PCM_FLOAT32 = 0, 1
 LAYOUT_TC, LAYOUT_CT = 0, 1
 
@@ -212,6 +219,13 @@ SIGNATURES = {
     "gsc_decode_crops": (ctypes.c_int, [ctypes.POINTER(ctypes.c_void_p), ctypes.c_int, ctypes.POINTER(GscCrop),
                                         ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_longlong, ctypes.c_void_p,
                                         ctypes.c_void_p, _LLP]),
+    "gsc_decode_crops_fmt": (ctypes.c_int, [ctypes.POINTER(ctypes.c_void_p), ctypes.c_int, ctypes.POINTER(GscCrop),
+                                            ctypes.c_int, ctypes.POINTER(GscCropFormat), ctypes.c_void_p,
+                                            ctypes.c_void_p, _LLP]),
+    "gsc_resample_table": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, _IP, _IP,
+                                          ctypes.POINTER(ctypes.POINTER(ctypes.c_int32))]),
+    "gsc_resample_prepare": (ctypes.c_int, [ctypes.c_int, ctypes.c_int]),
+    "gsc_resample_tile": (ctypes.c_int, []),
     "gsc_stream_decode_samples": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_longlong, ctypes.c_longlong, _I16P]),
     "gsc_decode_crops_variant": (ctypes.c_int, [ctypes.c_int]),
     "gsc_decode_indexed": (ctypes.c_int, [_U8P, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,

@@ -204,6 +204,11 @@ int set_stream_of_checkpoint(const SetLayout& lay, int64_t c);
 
 // One crop on the device: its stream's slabs and their sizes, the clipped
 // sample range, the frames [f0, f1) it crosses and its first piece.
+// What follows piece0 is read by crop_resample_kernel alone (gsc_decode_resample.hip):
+// there `begin` is in source samples, `count` in output samples, [f0, f1) are
+// the frames of the source range [src_begin, src_end) the filter reads inside
+// the stream, and rate_up / rate_down, half_taps and table are the resampler
+// of the stream's rate (half_taps 0: none, the samples pass as they are).
 struct CropJob {
     const ResFrame* frames;
     const uint64_t* cps;
@@ -213,6 +218,10 @@ struct CropJob {
     int64_t ncp, nwords, ncb, natt;
     int64_t begin, count;
     int32_t nframes, f0, f1, piece0;
+    int64_t src_begin, src_end;
+    const int32_t* table;  // [rate_up][2 * half_taps] on the device
+    int32_t rate_up, rate_down, half_taps;  // Fo / g, Fi / g, T
+    int32_t src_ch, out_ch;
 };
 
 // One frame of one crop: the checkpoint segments [seg0, seg0 + nseg) of the
@@ -235,6 +244,12 @@ struct PlanCrop {
     int stream;
     int64_t begin, count;  // count clipped to the stream's end
     int f0, f1, piece0;
+    // plan_crops_fmt: the source samples the crop reads inside its stream (the
+    // filter's reach on both sides of its outputs, clipped to [0, samples)), which
+    // [f0, f1) then cover, and the stream's resampler.  The phase of output 0 is
+    // (begin * rate_up) mod rate_up = 0 for every crop: `begin` is a whole sample.
+    int64_t src_begin = 0, src_end = 0;
+    int rate_up = 1, rate_down = 1, half_taps = 0;
 };
 struct CropPlan {
     std::vector<PlanCrop> crops;
@@ -246,5 +261,39 @@ struct CropPlan {
 // bad stream index and streams whose channel counts differ.
 int plan_crops(const Index* const* ixs, int nstreams, const Crop* crops, int ncrops, int64_t length, CropPlan* plan,
                std::string* err);
+
+// ---- crops at a common rate and channel count (gsc_decode_resample.hip) ------
+// The resampler of one pair of rates (include/soundchunks.h has the
+// definition): phases = Fo / g rows of taps = 2 T coefficients that sum to 2^24.
+constexpr int kResampleZeros = 16;       // zero crossings per side
+constexpr int kResampleShift = 24;       // a row sums to 1 << kResampleShift
+constexpr int kResampleMaxTaps = 512;
+constexpr int64_t kResampleMaxBytes = int64_t(16) << 20;
+constexpr int kResampleTile = 512;       // output samples of one workgroup
+// int16 source samples (all source channels) one workgroup keeps in LDS
+constexpr int kResampleSrcCap = 24 * 1024;
+struct ResampleShape {
+    int phases = 1, step = 1, half_taps = 0;  // Fo / g, Fi / g, T
+    int taps() const { return 2 * half_taps; }
+};
+// Refuses (-1, *err, both rates named) a rate <= 0, more than kResampleMaxTaps
+// taps and a table of more than kResampleMaxBytes.
+int resample_shape(int in_rate, int out_rate, ResampleShape* shape, std::string* err);
+// The table of a pair, built on first use and kept for the life of the
+// process; the pointer stays valid and what it points to is never written again.
+const int32_t* resample_table(int in_rate, int out_rate, ResampleShape* shape, std::string* err);
+// Outputs at out_rate from source position `begin` before the source position
+// reaches `samples`: ceil((samples - begin) * phases / step).
+int64_t resample_outputs(int64_t samples, int64_t begin, const ResampleShape& s);
+
+// plan_crops for gsc_decode_crops_fmt: counts are output samples at out_rate
+// (0: every stream keeps its rate), clipped where the source position reaches
+// the stream's end.  out_channels 0: the streams must agree, as in plan_crops;
+// otherwise a stream must have out_channels channels or one, or out_channels is
+// one.  Also refused: a pair of rates resample_shape refuses, and a filter
+// whose reach times the stream's channels exceeds kResampleSrcCap.  No pieces:
+// the kernel unpacks what it needs itself.
+int plan_crops_fmt(const Index* const* ixs, int nstreams, const Crop* crops, int ncrops, int64_t length, int out_rate,
+                   int out_channels, CropPlan* plan, std::string* err);
 
 }  // namespace gsc

@@ -15,8 +15,10 @@
 #include <chrono>
 #include <cstdlib>
 #include <cstring>
+#include <map>
 #include <memory>
 #include <mutex>
+#include <tuple>
 
 #include "../../include/soundchunks.h"
 #include "gsc_decode.h"
@@ -47,6 +49,8 @@ extern "C" hipError_t gsc_launch_crop_synth(const gsc::CropJob* jobs, int ncrops
                                             void* out, hipStream_t st);
 extern "C" hipError_t gsc_launch_crop_fused(const gsc::CropJob* jobs, int ncrops, int64_t length, int channels,
                                             int is_float, int planar, int tile_len, void* out, hipStream_t st);
+extern "C" hipError_t gsc_launch_crop_resample(const gsc::CropJob* jobs, int ncrops, int64_t length, int channels,
+                                               int is_float, int planar, int src_samples, void* out, hipStream_t st);
 
 struct gsc_index {
     gsc::Index ix;
@@ -283,6 +287,37 @@ int decode_parts(const std::vector<Part>& parts, int16_t** pcm, size_t* pcm_len,
     *pcm = host_out;
     *pcm_len = size_t(nout);
     tim->total_ms += now_ms() - t_begin;
+    return 0;
+}
+
+// The device copies of the resamplers' tables (resample_table): one per device
+// and reduced pair of rates, uploaded on first use with a blocking copy and
+// kept, never written again and never freed, for the life of the process, so
+// that crop calls on any HIP stream may read them without ordering.
+int device_resample_table(int in_rate, int out_rate, const int32_t** table) {
+    ResampleShape sh;
+    std::string err;
+    const int32_t* host = resample_table(in_rate, out_rate, &sh, &err);
+    if (!host) return set_last_error(err);
+    if (require_device() != 0) return -1;
+    int dev = 0;
+    DEC_TRY(hipGetDevice(&dev));
+    static std::mutex mu;
+    static std::map<std::tuple<int, int, int>, const int32_t*> tables;
+    std::lock_guard<std::mutex> lock(mu);
+    const int32_t*& slot = tables[std::make_tuple(dev, sh.phases, sh.step)];
+    if (!slot) {
+        const size_t bytes = size_t(sh.phases) * size_t(sh.taps()) * sizeof(int32_t);
+        int32_t* p = nullptr;
+        DEC_TRY(hipMalloc(reinterpret_cast<void**>(&p), bytes));
+        const hipError_t e = hipMemcpy(p, host, bytes, hipMemcpyHostToDevice);
+        if (e != hipSuccess) {
+            (void)hipFree(p);
+            return set_last_error(std::string("gsc resample: table upload: ") + hipGetErrorString(e));
+        }
+        slot = p;
+    }
+    *table = slot;
     return 0;
 }
 
@@ -887,6 +922,109 @@ int gsc_decode_crops(gsc_stream* const* streams, int nstreams, const gsc_crop* c
     t_dtim.h2d_bytes = (long long)desc_bytes;
     t_dtim.frames = int(npc);
     t_dtim.symbols = plan.slots * kDecodeS;
+    t_dtim.samples = int64_t(ncrops) * length * C;
+    t_dtim.total_ms = now_ms() - t_begin;
+    return report();
+}
+
+int gsc_resample_tile(void) { return kResampleTile; }
+
+int gsc_resample_table(int in_rate, int out_rate, int* phases, int* taps, const int32_t** coeff) {
+    ResampleShape sh;
+    std::string err;
+    const int32_t* t = resample_table(in_rate, out_rate, &sh, &err);
+    if (!t) return set_last_error(err);
+    if (phases) *phases = sh.phases;
+    if (taps) *taps = sh.taps();
+    if (coeff) *coeff = t;
+    return 0;
+}
+
+int gsc_resample_prepare(int in_rate, int out_rate) {
+    const int32_t* t = nullptr;
+    return in_rate == out_rate && in_rate > 0 ? 0 : device_resample_table(in_rate, out_rate, &t);
+}
+
+int gsc_decode_crops_fmt(gsc_stream* const* streams, int nstreams, const gsc_crop* crops, int ncrops,
+                         const gsc_crop_format* fmt, void* dst_device, void* hip_stream, long long* written) {
+    const double t_begin = now_ms();
+    t_dtim = gsc_decode_timing{};
+    if (!fmt) return set_last_error("gsc_decode_crops_fmt: format is null");
+    if (!streams || nstreams <= 0) return set_last_error("gsc_decode_crops_fmt: no streams");
+    if (fmt->dtype != GSC_PCM_INT16 && fmt->dtype != GSC_PCM_FLOAT32)
+        return set_last_error("gsc_decode_crops_fmt: unknown dtype");
+    if (fmt->layout != GSC_LAYOUT_TC && fmt->layout != GSC_LAYOUT_CT)
+        return set_last_error("gsc_decode_crops_fmt: unknown layout");
+    if (!dst_device) return set_last_error("gsc_decode_crops_fmt: dst_device is null");
+    std::vector<const Index*> ixs(static_cast<size_t>(nstreams), nullptr);
+    for (int s = 0; s < nstreams; ++s) {
+        if (!streams[s]) return set_last_error("gsc_decode_crops_fmt: stream " + std::to_string(s) + " is null");
+        ixs[size_t(s)] = &streams[s]->idx.ix;
+    }
+    std::vector<Crop> cr(static_cast<size_t>(std::max(ncrops, 0)));
+    if (ncrops > 0 && !crops) return set_last_error("gsc_decode_crops_fmt: crops is null");
+    for (int i = 0; i < ncrops; ++i) cr[size_t(i)] = Crop{crops[i].stream, crops[i].begin, crops[i].count};
+    const int64_t length = fmt->length;
+    CropPlan plan;
+    std::string err;
+    if (plan_crops_fmt(ixs.data(), nstreams, cr.data(), ncrops, length, fmt->out_rate, fmt->out_channels, &plan,
+                       &err) != 0)
+        return set_last_error(err);
+    if (require_device() != 0) return -1;
+    int dev = 0;
+    DEC_TRY(hipGetDevice(&dev));
+    for (int s = 0; s < nstreams; ++s)
+        if (streams[s]->device != dev)
+            return set_last_error("gsc_decode_crops_fmt: stream " + std::to_string(s) + " lives on device " +
+                                  std::to_string(streams[s]->device) + ", the calling thread is bound to device " +
+                                  std::to_string(dev));
+    auto report = [&] {  // only once everything is enqueued: a failed call reports no output
+        for (int i = 0; i < ncrops; ++i)
+            if (written) written[i] = plan.crops[size_t(i)].count;
+        return 0;
+    };
+    if (ncrops == 0 || length == 0) return report();
+    const int C = plan.channels;
+    if (C <= 0 || C > 255 || length > (int64_t(1) << 40) / (int64_t(ncrops) * C))
+        return set_last_error("gsc_decode_crops_fmt: output too large for one call");
+    // the tables of the rates this call resamples from: the one place that may upload and block (first use)
+    std::vector<const int32_t*> tables(static_cast<size_t>(nstreams), nullptr);
+    for (const PlanCrop& pc : plan.crops)
+        if (pc.half_taps > 0 && !tables[size_t(pc.stream)] &&
+            device_resample_table(ixs[size_t(pc.stream)]->rate, fmt->out_rate, &tables[size_t(pc.stream)]) != 0)
+            return -1;
+    hipStream_t hs = static_cast<hipStream_t>(hip_stream);
+    const size_t njob = size_t(ncrops);
+    const size_t desc_bytes = (njob * sizeof(CropJob) + 15) & ~size_t(15);
+    std::vector<unsigned char> host(desc_bytes, 0);
+    CropJob* hj = reinterpret_cast<CropJob*>(host.data());
+    int64_t src_samples = 1;  // the LDS of a workgroup: the widest source span of a full tile, all channels
+    for (size_t i = 0; i < njob; ++i) {
+        const PlanCrop& pc = plan.crops[i];
+        const gsc_stream& st = *streams[pc.stream];
+        const int sch = st.idx.ix.channels;
+        hj[i] = CropJob{st.frames, st.cps,   st.words, st.cb,    st.att, st.ncp, st.nwords, st.ncb,
+                        st.natt,   pc.begin, pc.count, int32_t(st.idx.ix.frames.size()),
+                        pc.f0,     pc.f1,    0,        pc.src_begin, pc.src_end, tables[size_t(pc.stream)],
+                        pc.rate_up, pc.rate_down, pc.half_taps, sch, C};
+        const int64_t tile = std::min<int64_t>(length, kResampleTile);
+        // rounded up, so that the kernel's outputs per pass come out as the whole tile
+        const int64_t reach = ((tile - 1) * pc.rate_down + pc.rate_up - 1) / pc.rate_up + 2 * pc.half_taps + 2;
+        src_samples = std::max(src_samples, std::min<int64_t>(reach * sch, kResampleSrcCap));
+    }
+    unsigned char* d_block = nullptr;
+    DEC_TRY(hipMallocAsync(reinterpret_cast<void**>(&d_block), desc_bytes, hs));
+    struct FreeAsync {
+        unsigned char* p;
+        hipStream_t s;
+        ~FreeAsync() { (void)hipFreeAsync(p, s); }
+    } guard{d_block, hs};
+    // pageable source, as in gsc_decode_crops
+    DEC_TRY(hipMemcpyAsync(d_block, host.data(), desc_bytes, hipMemcpyHostToDevice, hs));
+    DEC_TRY(gsc_launch_crop_resample(reinterpret_cast<const CropJob*>(d_block), ncrops, length, C,
+                                     fmt->dtype == GSC_PCM_FLOAT32, fmt->layout == GSC_LAYOUT_CT, int(src_samples),
+                                     dst_device, hs));
+    t_dtim.h2d_bytes = (long long)desc_bytes;
     t_dtim.samples = int64_t(ncrops) * length * C;
     t_dtim.total_ms = now_ms() - t_begin;
     return report();

@@ -44,19 +44,6 @@ namespace {
 constexpr int kCropUnpackThreads = 256;
 constexpr int kCropSynthThreads = 256;
 
-// Segment seg of frame f of a crop's stream to o[0 .. kDecodeS); false (nothing
-// written) when the segment or its checkpoint lies outside the stream's slabs.
-__device__ __forceinline__ bool crop_unpack_one(const CropJob& job, const ResFrame& f, int64_t seg, uint16_t* o) {
-    if (seg < 0 || seg > f.nsym / kDecodeS) return false;
-    const int64_t s0 = seg * kDecodeS;
-    if (s0 >= f.nsym) return false;
-    const int n = (int)(f.nsym - s0 < kDecodeS ? f.nsym - s0 : kDecodeS);
-    const int64_t c = f.cp_first + seg;
-    if (c < 0 || c >= job.ncp || f.bs_off < 0) return false;
-    unpack_segment(job.words, job.nwords, f.bs_off, job.cps[c], f.ver, f.count, n, o);
-    return true;
-}
-
 __global__ __launch_bounds__(kCropUnpackThreads) void crop_unpack_kernel(const CropJob* __restrict__ jobs, int ncrops,
                                                                          const CropPiece* __restrict__ pieces,
                                                                          int npieces, uint16_t* __restrict__ sym,
@@ -70,22 +57,6 @@ __global__ __launch_bounds__(kCropUnpackThreads) void crop_unpack_kernel(const C
     const CropJob& job = jobs[pc.crop];
     if (pc.frame < 0 || pc.frame >= job.nframes) return;
     (void)crop_unpack_one(job, job.frames[pc.frame], pc.seg0 + k, sym + slot * kDecodeS);
-}
-
-template <typename T>
-__device__ __forceinline__ T to_out(int16_t v);
-template <>
-__device__ __forceinline__ int16_t to_out<int16_t>(int16_t v) {
-    return v;
-}
-template <>
-__device__ __forceinline__ float to_out<float>(int16_t v) {
-    return (float)v * (1.0f / 32768.0f);
-}
-
-// the frame of [f0, f1) that holds sample s: the last one whose first sample is <= s
-__device__ __forceinline__ int crop_frame_of(const CropJob& job, int f0, int f1, int64_t s) {
-    return last_le(f0, f1 - 1, s, [&](int i) { return job.frames[i].first_sample; });
 }
 
 // The symbol word of (symbol row q, channel k) of frame fr of a crop, from the
@@ -104,39 +75,6 @@ __device__ __forceinline__ bool crop_symbol(const CropJob& job, const ResFrame& 
     if (slot < 0 || slot >= nslots) return false;
     *w = sym[slot * kDecodeS + (si % kDecodeS)];
     return true;
-}
-
-// the tables of a crop's stream in global memory
-__device__ __forceinline__ TableSlabs crop_tables(const CropJob& job) {
-    return TableSlabs{job.cb, job.ncb, job.att, job.natt};
-}
-
-// Element l of a run of nt samples x channels that starts at sample ta of a
-// crop's row: its sample, its channel, and its place in the output.
-template <bool PLANAR>
-__device__ __forceinline__ int64_t crop_elem(int l, int nt, int64_t ta, int channels, int64_t length, int64_t out_base,
-                                             int64_t* t, int* k) {
-    if (PLANAR) {
-        *k = l / nt;
-        *t = ta + (l - *k * nt);
-        return out_base + (int64_t)*k * length + *t;
-    }
-    *t = ta + l / channels;
-    *k = l % channels;
-    return out_base + *t * channels + *k;
-}
-
-// value(t, k) for samples [ta, tb) of a crop's row, every channel, by a whole workgroup
-template <typename T, bool PLANAR, typename Value>
-__device__ __forceinline__ void crop_write_run(int64_t ta, int64_t tb, int channels, int64_t length, int64_t out_base,
-                                               T* __restrict__ out, int64_t nout, int tid, int threads, Value value) {
-    const int nt = (int)(tb - ta);
-    for (int l = tid; l < nt * channels; l += threads) {
-        int64_t t;
-        int k;
-        const int64_t oi = crop_elem<PLANAR>(l, nt, ta, channels, length, out_base, &t, &k);
-        if (oi >= 0 && oi < nout) out[oi] = to_out<T>(value(t, k));
-    }
 }
 
 template <typename T, bool PLANAR>
@@ -340,13 +278,6 @@ hipError_t launch_fused(const CropJob* jobs, int ncrops, int64_t length, int cha
                        jobs, ncrops, length, channels, tile_len, (int)tiles, static_cast<T*>(out),
                        (int64_t)ncrops * length * channels);
     return hipGetLastError();
-}
-
-// f(T{}, std::bool_constant<PLANAR>{}) for the output's element type and layout
-template <typename F>
-hipError_t dispatch_out(int is_float, int planar, F f) {
-    if (is_float) return planar ? f(float{}, std::true_type{}) : f(float{}, std::false_type{});
-    return planar ? f(int16_t{}, std::true_type{}) : f(int16_t{}, std::false_type{});
 }
 
 }  // namespace

@@ -234,9 +234,10 @@ class StreamSet:
     def streams(self):
         return [self[i] for i in range(len(self))]
 
-    def decode_crops(self, crops, length: int, dtype=None, layout: str = "TC", out=None):
+    def decode_crops(self, crops, length: int, dtype=None, layout: str = "TC", out=None, rate=None, channels=None):
         """``Decoder.decode_crops(self.streams, ...)``: crop stream indices count the set's members."""
-        return Decoder.decode_crops(self.streams, crops, length, dtype=dtype, layout=layout, out=out)
+        return Decoder.decode_crops(self.streams, crops, length, dtype=dtype, layout=layout, out=out, rate=rate,
+                                    channels=channels)
 
     def close(self) -> None:
         if getattr(self, "_h", None):
@@ -313,18 +314,58 @@ class Decoder:
         return Decoder.CROP_VARIANTS[_lib.load().gsc_decode_crops_variant(v)]
 
     @staticmethod
-    def decode_crops(streams, crops, length: int, dtype=None, layout: str = "TC", out=None):
+    def resample_tile() -> int:
+        """Output samples of one workgroup of the resampling crop kernel."""
+        return _lib.load().gsc_resample_tile()
+
+    @staticmethod
+    def resample_table(in_rate: int, out_rate: int) -> np.ndarray:
+        """The resampler of a pair of rates (include/soundchunks.h has the
+        definition): int32 array [phases, taps], every row summing to 2**24.
+        Host only; a pair the library refuses raises with both rates named."""
+        lib = _lib.load()
+        phases, taps = ctypes.c_int(0), ctypes.c_int(0)
+        coeff = ctypes.POINTER(ctypes.c_int32)()
+        _lib.check(lib.gsc_resample_table(int(in_rate), int(out_rate), ctypes.byref(phases), ctypes.byref(taps),
+                                          ctypes.byref(coeff)))
+        return np.ctypeslib.as_array(coeff, shape=(phases.value, taps.value)).copy()
+
+    @staticmethod
+    def prepare_resample(in_rate: int, out_rate: int, device=None) -> None:
+        """Builds and uploads the table of a pair of rates now (a blocking copy),
+        so that no later ``decode_crops(..., rate=out_rate)`` has to."""
+        import torch
+
+        with torch.cuda.device(torch.cuda.current_device() if device is None else device):
+            _lib.check(_lib.load().gsc_resample_prepare(int(in_rate), int(out_rate)))
+
+    @staticmethod
+    def decode_crops(streams, crops, length: int, dtype=None, layout: str = "TC", out=None, rate=None,
+                     channels=None):
         """``crops``: (stream index, begin, count) in per-channel samples.
         Returns (tensor on the streams' device, [B, length, C] for layout "TC"
         or [B, C, length] for "CT", int16 or float32 = int16 / 32768; written
         lengths).  Crop i fills row i, clipped at its stream's end, zero after.
-        The work is enqueued on torch's current stream; nothing is synchronised."""
+        The work is enqueued on torch's current stream; nothing is synchronised.
+
+        ``rate`` (Hz) and ``channels`` bring every row to one sample rate and
+        channel count on the device, whatever its stream's own; ``begin`` then
+        stays in source samples of the crop's stream, ``count`` and ``length``
+        are output samples at ``rate``.  ``rate=None``: no resampling;
+        ``channels=None``: the streams' count, which must agree.  The first call
+        that meets a new pair of rates on a device uploads its table with a
+        blocking copy (``prepare_resample`` does it ahead of time)."""
         import torch
 
         lib = _lib.load()
         streams, crops = list(streams), [tuple(int(v) for v in c) for c in crops]
         if not streams:
             raise _lib.GscError("decode_crops: no streams")
+        fmt = rate is not None or channels is not None
+        if rate is not None and int(rate) <= 0:
+            raise _lib.GscError(f"decode_crops: rate {rate} Hz: a rate must be positive")
+        if channels is not None and int(channels) <= 0:
+            raise _lib.GscError(f"decode_crops: channels {channels}")
         dtype = torch.int16 if dtype is None else dtype
         if dtype not in (torch.int16, torch.float32):
             raise _lib.GscError(f"decode_crops: dtype {dtype} is neither torch.int16 nor torch.float32")
@@ -333,7 +374,7 @@ class Decoder:
         length = int(length)
         if length < 0:
             raise _lib.GscError(f"decode_crops: length {length}")
-        ch = streams[0].channels
+        ch = streams[0].channels if channels is None else int(channels)
         device = torch.device("cuda", streams[0].device)
         shape = (len(crops), length, ch) if layout == "TC" else (len(crops), ch, length)
         if out is None:
@@ -349,12 +390,18 @@ class Decoder:
         hs = (ctypes.c_void_p * len(streams))(*[s._handle() for s in streams])
         cr = (_lib.GscCrop * max(1, len(crops)))(*[_lib.GscCrop(*c) for c in crops])
         written = (ctypes.c_longlong * max(1, len(crops)))()
+        pcm = _lib.PCM_FLOAT32 if dtype == torch.float32 else _lib.PCM_INT16
+        lay = _lib.LAYOUT_CT if layout == "CT" else _lib.LAYOUT_TC
         with torch.cuda.device(device):
-            _lib.check(lib.gsc_decode_crops(hs, len(streams), cr, len(crops),
-                                            _lib.PCM_FLOAT32 if dtype == torch.float32 else _lib.PCM_INT16,
-                                            _lib.LAYOUT_CT if layout == "CT" else _lib.LAYOUT_TC, length,
-                                            dst.data_ptr(),
-                                            ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream), written))
+            hip_stream = ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+            if fmt:
+                f = _lib.GscCropFormat(pcm, lay, length, 0 if rate is None else int(rate),
+                                       0 if channels is None else int(channels))
+                _lib.check(lib.gsc_decode_crops_fmt(hs, len(streams), cr, len(crops), ctypes.byref(f),
+                                                    dst.data_ptr(), hip_stream, written))
+            else:
+                _lib.check(lib.gsc_decode_crops(hs, len(streams), cr, len(crops), pcm, lay, length, dst.data_ptr(),
+                                                hip_stream, written))
         return out, [int(written[i]) for i in range(len(crops))]
 
     def decode(self, gsc: bytes, frame_begin: int = 0, frame_end: int = -1, table: bytes | None = None):
