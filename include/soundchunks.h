@@ -477,6 +477,82 @@ int gsc_encode_prepared_files_with_tables(gsc_prepared *p, int frame_begin, int 
                                           size_t *out_len, size_t *file_bytes, uint8_t **tables, size_t *tables_len,
                                           size_t *table_bytes);
 
+/* ---- bound streams: crops whose list lives on the device ----------------------- */
+/* gsc_decode_crops and gsc_decode_crops_fmt plan every crop on the host and
+ * upload the plan, so the crop list must exist on the host and every call
+ * allocates and copies.  A binding describes the streams of a loader once on
+ * the device; gsc_crop_binding_decode then takes the crops from device memory
+ * and does nothing on the host but check its arguments and launch one kernel,
+ * which plans each crop itself.
+ *
+ * gsc_crop_binding_create may block, allocate and copy: it uploads one
+ * descriptor per stream (its slabs and their sizes, its frames, samples and
+ * channels, its resampler for out_rate) and, for every distinct source rate,
+ * the resampler's table (as gsc_resample_prepare).  out_rate and out_channels
+ * are gsc_crop_format's: out_rate 0 resamples nothing, out_channels 0 takes
+ * the streams' count, which must then agree; with both 0 the binding runs the
+ * fused kernel of gsc_decode_crops, otherwise the kernel of
+ * gsc_decode_crops_fmt.  Refused (NULL and gsc_last_error, the stream named):
+ * what gsc_decode_crops and gsc_decode_crops_fmt refuse per stream, i.e.
+ * channel counts that do not agree or do not map, a pair of rates without a
+ * resampler, a filter too wide for a workgroup, a stream of more than 2^40
+ * samples, and a stream on another device than the calling thread's; also no
+ * streams at all.  Members of sets and streams opened on their own mix
+ * freely.  The binding borrows the streams: they must stay open until
+ * gsc_crop_binding_free, which first waits for the device's queued work.
+ *
+ * gsc_crop_binding_decode.  crops_device is ncrops x {stream, begin, count} as
+ * int64 in device memory, stream counting the binding's streams.  Units are
+ * gsc_decode_crops_fmt's: `begin` in source samples of the crop's stream,
+ * `count` and `length` in output samples at out_rate (the stream's own rate
+ * without one).  dst_device, dtype, layout and the clipping at a stream's end
+ * are gsc_decode_crops'.  written_device (may be NULL) is ncrops int64 in
+ * device memory: the clipped length of each crop, as gsc_decode_crops reports
+ * it on the host, stored once per crop.
+ *
+ * Bad crops.  The call cannot refuse a value it never reads, so a bad crop
+ * costs its own row and nothing else: the row is zero over the whole length,
+ * written[i] is -1, every other row is what it would be without it.  A crop is
+ * bad when its stream is outside [0, nstreams), when begin < 0 or begin > its
+ * stream's samples, or when count < 0 or count > length: gsc_decode_crops'
+ * per-crop refusals.  The kernels check or clamp every index they derive.
+ *
+ * The call contract.  The call reads no crop on the host, allocates nothing,
+ * copies nothing, synchronises nothing and keeps no scratch between calls:
+ * calls with one binding on several HIP streams share only memory that nobody
+ * writes.  It checks dtype, layout, the pointers and that ncrops x length x
+ * channels and length x the largest decimation step stay within 2^40, that the
+ * calling thread is on the binding's device, and launches on hip_stream;
+ * ncrops == 0 or length == 0 launches nothing and leaves written_device as it
+ * is.  Everything is ordered with hip_stream alone, so crops_device may be
+ * written by earlier work of that stream, and the call may be recorded into a
+ * HIP graph and replayed with new crops in the same memory (the library has no
+ * capture helper and tests none).
+ *
+ * gsc_crop_binding_last_call: the runtime calls of the calling thread's last
+ * gsc_crop_binding_decode, counted where they are made, and its host time. */
+typedef struct gsc_crop_binding gsc_crop_binding;
+typedef struct {
+    int launches, allocations, copies, synchronisations;
+    double host_ms;
+} gsc_crop_call_stats;
+gsc_crop_binding *gsc_crop_binding_create(gsc_stream *const *streams, int nstreams, int out_rate, int out_channels);
+int gsc_crop_binding_decode(gsc_crop_binding *b, const long long *crops_device, int ncrops, int dtype, int layout,
+                            long long length, void *dst_device, long long *written_device, void *hip_stream);
+void gsc_crop_binding_last_call(gsc_crop_call_stats *stats);
+void gsc_crop_binding_free(gsc_crop_binding *b);
+/* The planner of the bound kernels for one crop, on the host and without a
+ * device (parity tests): crop (stream, begin, count) of a call over nstreams
+ * streams with `length`, the crop's stream being ix, at out_rate (0: its own).
+ * Returns 0 for a good crop, 1, 2 or 3 for a bad stream index, begin or count
+ * (*written = -1 then), < 0 and gsc_last_error for a pair of rates without a
+ * resampler.  For a good crop *written is the clipped count, [*src_begin,
+ * *src_end) the source samples its filter reads inside the stream and [*f0,
+ * *f1) the frames that hold them; all 0 when nothing is written. */
+int gsc_crop_plan_model(const gsc_index *ix, int nstreams, int stream, long long begin, long long count,
+                        long long length, int out_rate, long long *written, int *f0, int *f1, long long *src_begin,
+                        long long *src_end);
+
 /* Timing of the last gsc_decode*, gsc_stream_open or crop call on the calling
  * thread (milliseconds).  h2d_bytes: the bytes that call uploaded. */
 typedef struct {

@@ -124,6 +124,13 @@ class GscCropFormat(ctypes.Structure):
                 ("out_rate", ctypes.c_int), ("out_channels", ctypes.c_int)]
 
 
+class GscCropCallStats(ctypes.Structure):
+    """Mirror of ``gsc_crop_call_stats``."""
+
+    _fields_ = [("launches", ctypes.c_int), ("allocations", ctypes.c_int), ("copies", ctypes.c_int),
+                ("synchronisations", ctypes.c_int), ("host_ms", ctypes.c_double)]
+
+
 PCM_INT16, PCM_FLOAT32 = 0, 1
 LAYOUT_TC, LAYOUT_CT = 0, 1
 
@@ -222,6 +229,16 @@ SIGNATURES = {
     "gsc_decode_crops_fmt": (ctypes.c_int, [ctypes.POINTER(ctypes.c_void_p), ctypes.c_int, ctypes.POINTER(GscCrop),
                                             ctypes.c_int, ctypes.POINTER(GscCropFormat), ctypes.c_void_p,
                                             ctypes.c_void_p, _LLP]),
+    "gsc_crop_binding_create": (ctypes.c_void_p, [ctypes.POINTER(ctypes.c_void_p), ctypes.c_int, ctypes.c_int,
+                                                  ctypes.c_int]),
+    "gsc_crop_binding_decode": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
+                                               ctypes.c_int, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_void_p,
+                                               ctypes.c_void_p]),
+    "gsc_crop_binding_last_call": (None, [ctypes.POINTER(GscCropCallStats)]),
+    "gsc_crop_binding_free": (None, [ctypes.c_void_p]),
+    "gsc_crop_plan_model": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_longlong,
+                                           ctypes.c_longlong, ctypes.c_longlong, ctypes.c_int, _LLP, _IP, _IP, _LLP,
+                                           _LLP]),
     "gsc_resample_table": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, _IP, _IP,
                                           ctypes.POINTER(ctypes.POINTER(ctypes.c_int32))]),
     "gsc_resample_prepare": (ctypes.c_int, [ctypes.c_int, ctypes.c_int]),

@@ -224,6 +224,24 @@ struct CropJob {
     int32_t src_ch, out_ch;
 };
 
+// One stream of a crop binding (gsc_crop_binding_create) on the device: what
+// of a CropJob does not depend on the crop.  The kernels of a bound call make
+// the CropJob of a crop from its (stream, begin, count) in device memory and
+// this (gsc_crop_plan.h), where the other calls load one the host planned.
+struct BoundStream {
+    const ResFrame* frames;
+    const uint64_t* cps;
+    const uint32_t* words;
+    const int16_t* cb;
+    const uint8_t* att;
+    int64_t ncp, nwords, ncb, natt;
+    int64_t samples;       // per channel
+    const int32_t* table;  // the resampler of the stream's rate for the binding's; null without one
+    int32_t nframes, channels;
+    int32_t rate_up, rate_down, half_taps;  // 1, 1, 0: the samples pass as they are
+    int32_t pad_;
+};
+
 // One frame of one crop: the checkpoint segments [seg0, seg0 + nseg) of the
 // frame are unpacked to segment slots [slot0, slot0 + nseg) of the call's
 // symbol scratch (kDecodeS words per slot).  A crop owns f1 - f0 pieces, one

@@ -9,6 +9,9 @@
 // (gsc_stream_set_open) keeps many streams in one Slabs, laid out by
 // set_layout (gsc_decode_set.cpp), their tables expanded on the device.  All
 // keep their device copies in a Slabs and describe a frame with frame_tables.
+// A crop binding (gsc_crop_binding_create) describes resident streams once on
+// the device; gsc_crop_binding_decode then takes the crops from device memory
+// and only launches: the kernels plan each crop themselves (gsc_crop_plan.h).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -21,6 +24,7 @@
 #include <tuple>
 
 #include "../../include/soundchunks.h"
+#include "gsc_crop_plan.h"
 #include "gsc_decode.h"
 #include "gsc_device.h"
 
@@ -51,6 +55,15 @@ extern "C" hipError_t gsc_launch_crop_fused(const gsc::CropJob* jobs, int ncrops
                                             int is_float, int planar, int tile_len, void* out, hipStream_t st);
 extern "C" hipError_t gsc_launch_crop_resample(const gsc::CropJob* jobs, int ncrops, int64_t length, int channels,
                                                int is_float, int planar, int src_samples, void* out, hipStream_t st);
+
+extern "C" hipError_t gsc_launch_crop_fused_bound(const gsc::BoundStream* streams, int nstreams, const int64_t* crops,
+                                                  int ncrops, int64_t length, int channels, int is_float, int planar,
+                                                  int tile_len, void* out, int64_t* written, hipStream_t st);
+extern "C" hipError_t gsc_launch_crop_resample_bound(const gsc::BoundStream* streams, int nstreams,
+                                                     const int64_t* crops, int ncrops, int64_t length, int channels,
+                                                     int is_float, int planar, int src_samples, void* out,
+                                                     int64_t* written, hipStream_t st);
+extern "C" hipError_t gsc_prepare_crop_resample_bound(int src_samples);
 
 struct gsc_index {
     gsc::Index ix;
@@ -361,6 +374,45 @@ struct gsc_stream_set {
     gsc::Slabs<gsc::ResFrame> slabs;
     std::unique_ptr<gsc_stream[]> members;
     int count = 0;
+};
+
+namespace gsc {
+namespace {
+
+// A resampler and a channel count that streams of a binding share: what the LDS of a workgroup depends on.
+struct BoundShape {
+    int rate_up, rate_down, half_taps, channels;
+    bool operator==(const BoundShape& o) const {
+        return rate_up == o.rate_up && rate_down == o.rate_down && half_taps == o.half_taps && channels == o.channels;
+    }
+};
+
+thread_local gsc_crop_call_stats t_bstat;  // the last gsc_crop_binding_decode
+
+}  // namespace
+}  // namespace gsc
+
+// The streams of a loader, described once on the device (BoundStream): what
+// gsc_crop_binding_decode needs to launch without looking at a crop.
+struct gsc_crop_binding {
+    int device = 0, nstreams = 0, channels = 0;
+    bool fmt = false;      // an output rate or channel count was given: the resampling kernel
+    int max_step = 1;      // the largest rate_down: bounds `length`
+    gsc::Dev<gsc::BoundStream> streams;
+    std::vector<gsc::BoundShape> shapes;  // the distinct ones of the streams
+
+    // The int16 source samples a workgroup of the resampling kernel keeps for a tile of `tile`
+    // outputs: the widest source span over the binding's streams, all channels (as gsc_decode_crops_fmt
+    // takes it over a call's crops).
+    int src_samples(int64_t tile) const {
+        int64_t n = 1;
+        for (const gsc::BoundShape& s : shapes) {
+            // rounded up, so that the kernel's outputs per pass come out as the whole tile
+            const int64_t reach = ((tile - 1) * s.rate_down + s.rate_up - 1) / s.rate_up + 2 * s.half_taps + 2;
+            n = std::max(n, std::min<int64_t>(reach * s.channels, gsc::kResampleSrcCap));
+        }
+        return int(n);
+    }
 };
 
 using namespace gsc;
@@ -1028,6 +1080,157 @@ int gsc_decode_crops_fmt(gsc_stream* const* streams, int nstreams, const gsc_cro
     t_dtim.samples = int64_t(ncrops) * length * C;
     t_dtim.total_ms = now_ms() - t_begin;
     return report();
+}
+
+int gsc_crop_plan_model(const gsc_index* ix, int nstreams, int stream, long long begin, long long count,
+                        long long length, int out_rate, long long* written, int* f0, int* f1, long long* src_begin,
+                        long long* src_end) {
+    if (!ix || out_rate < 0 || length < 0) return set_last_error("gsc_crop_plan_model: invalid argument");
+    const Index& x = ix->ix;
+    ResampleShape sh;  // a stream without samples has no rate of its own, as in plan_crops_fmt
+    std::string err;
+    if (out_rate != 0 && x.rate != out_rate && x.samples > 0 && resample_shape(x.rate, out_rate, &sh, &err) != 0)
+        return set_last_error(err);
+    if (x.samples > (int64_t(1) << 40) || length > (int64_t(1) << 40) / sh.step)
+        return set_last_error("gsc_crop_plan_model: too long for one call");
+    CropSpan sp{0, 0, 0, 0, 0};
+    int status = crop_stream_status(stream, nstreams);
+    if (status == kCropGood)
+        status = crop_plan_one(begin, count, length, x.samples, int32_t(x.frames.size()), sh.phases, sh.step,
+                               sh.half_taps, [&](int32_t i) { return x.frames[size_t(i)].first_sample; }, &sp);
+    if (written) *written = status == kCropGood ? sp.count : -1;
+    if (f0) *f0 = sp.f0;
+    if (f1) *f1 = sp.f1;
+    if (src_begin) *src_begin = sp.src_begin;
+    if (src_end) *src_end = sp.src_end;
+    return status;
+}
+
+gsc_crop_binding* gsc_crop_binding_create(gsc_stream* const* streams, int nstreams, int out_rate, int out_channels) {
+    auto fail = [](const std::string& what) {
+        set_last_error(what);
+        return static_cast<gsc_crop_binding*>(nullptr);
+    };
+    auto named = [](int s) { return "gsc crop binding: stream " + std::to_string(s); };
+    if (!streams || nstreams <= 0) return fail("gsc crop binding: no streams");
+    if (out_rate < 0)
+        return fail("gsc resample: output rate " + std::to_string(out_rate) + " Hz: a rate must be positive");
+    if (out_channels < 0 || out_channels > 255) return fail("gsc crop binding: invalid argument");
+    for (int s = 0; s < nstreams; ++s)
+        if (!streams[s]) return fail(named(s) + " is null");
+    if (require_device() != 0) return nullptr;
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return fail("gsc crop binding: hipGetDevice failed");
+    std::unique_ptr<gsc_crop_binding> b(new gsc_crop_binding());
+    b->device = dev;
+    b->nstreams = nstreams;
+    b->fmt = out_rate != 0 || out_channels != 0;
+    b->channels = out_channels ? out_channels : streams[0]->idx.ix.channels;
+    if (b->channels <= 0 || b->channels > 255) return fail("gsc crop binding: invalid argument");
+    std::vector<BoundStream> desc(static_cast<size_t>(nstreams));
+    for (int s = 0; s < nstreams; ++s) {
+        const gsc_stream& st = *streams[s];
+        const Index& ix = st.idx.ix;
+        const int cs = ix.channels;
+        // plan_crops' and plan_crops_fmt's refusals per stream, and gsc_decode_crops' of another device
+        if (out_channels == 0 && cs != b->channels)
+            return fail(named(s) + " has " + std::to_string(cs) + " channels, stream 0 has " +
+                        std::to_string(b->channels));
+        if (out_channels != 0 && cs != out_channels && cs != 1 && out_channels != 1)
+            return fail(named(s) + " has " + std::to_string(cs) + " channels, which do not map to " +
+                        std::to_string(out_channels) + " (equal counts, a mono stream, or a mono output)");
+        ResampleShape sh;
+        const int32_t* table = nullptr;
+        if (out_rate != 0 && ix.rate != out_rate && ix.samples > 0) {
+            std::string e;
+            if (resample_shape(ix.rate, out_rate, &sh, &e) != 0) return fail(named(s) + ": " + e);
+        }
+        if ((int64_t(sh.taps()) + 2) * std::max(cs, 1) > kResampleSrcCap)
+            return fail(named(s) + ": " + std::to_string(sh.taps()) + " taps x " + std::to_string(cs) +
+                        " channels exceed the " + std::to_string(kResampleSrcCap) + " source samples of one workgroup");
+        if (ix.samples > (int64_t(1) << 40) || ix.frames.size() >= (size_t(1) << 31))
+            return fail(named(s) + ": too long for one call");
+        if (st.device != dev)
+            return fail(named(s) + " lives on device " + std::to_string(st.device) +
+                        ", the calling thread is bound to device " + std::to_string(dev));
+        // every table a call will read is on the device before the first call
+        if (sh.half_taps > 0 && device_resample_table(ix.rate, out_rate, &table) != 0) {
+            set_last_error(named(s) + ": " + gsc_last_error());
+            return nullptr;
+        }
+        desc[size_t(s)] = BoundStream{st.frames, st.cps,     st.words,  st.cb,        st.att,
+                                      st.ncp,    st.nwords,  st.ncb,    st.natt,      ix.samples,
+                                      table,     int32_t(ix.frames.size()), cs,       sh.phases,
+                                      sh.step,   sh.half_taps, 0};
+        b->max_step = std::max(b->max_step, sh.step);
+        const BoundShape shape{sh.phases, sh.step, sh.half_taps, cs};
+        if (std::find(b->shapes.begin(), b->shapes.end(), shape) == b->shapes.end()) b->shapes.push_back(shape);
+    }
+    const auto hip_failed = [&](hipError_t e, const char* what) {
+        if (e != hipSuccess) set_last_error(std::string("gsc crop binding: ") + what + ": " + hipGetErrorString(e));
+        return e != hipSuccess;
+    };
+    if (hip_failed(b->streams.alloc(desc.size()), "hipMalloc") ||
+        hip_failed(hipMemcpy(b->streams.p, desc.data(), desc.size() * sizeof(BoundStream), hipMemcpyHostToDevice),
+                   "hipMemcpy") ||
+        (b->fmt && hip_failed(gsc_prepare_crop_resample_bound(b->src_samples(kResampleTile)), "LDS limit")))
+        return nullptr;
+    return b.release();
+}
+
+int gsc_crop_binding_decode(gsc_crop_binding* b, const long long* crops_device, int ncrops, int dtype, int layout,
+                            long long length, void* dst_device, long long* written_device, void* hip_stream) {
+    const double t_begin = now_ms();
+    gsc_crop_call_stats& stats = t_bstat = gsc_crop_call_stats{};
+    if (!b) return set_last_error("gsc_crop_binding_decode: binding is null");
+    if (dtype != GSC_PCM_INT16 && dtype != GSC_PCM_FLOAT32)
+        return set_last_error("gsc_crop_binding_decode: unknown dtype");
+    if (layout != GSC_LAYOUT_TC && layout != GSC_LAYOUT_CT)
+        return set_last_error("gsc_crop_binding_decode: unknown layout");
+    if (ncrops < 0 || length < 0) return set_last_error("gsc_crop_binding_decode: invalid argument");
+    if (ncrops > 0 && length > 0) {
+        if (!crops_device) return set_last_error("gsc_crop_binding_decode: crops_device is null");
+        if (!dst_device) return set_last_error("gsc_crop_binding_decode: dst_device is null");
+        const int C = b->channels;
+        if (length > (int64_t(1) << 40) / (int64_t(ncrops) * C) || length > (int64_t(1) << 40) / b->max_step)
+            return set_last_error("gsc_crop_binding_decode: output too large for one call");
+        int dev = 0;
+        DEC_TRY(hipGetDevice(&dev));
+        if (dev != b->device)
+            return set_last_error("gsc_crop_binding_decode: the binding lives on device " + std::to_string(b->device) +
+                                  ", the calling thread is bound to device " + std::to_string(dev));
+        hipStream_t hs = static_cast<hipStream_t>(hip_stream);
+        const int is_float = dtype == GSC_PCM_FLOAT32, planar = layout == GSC_LAYOUT_CT;
+        const int64_t* crops = reinterpret_cast<const int64_t*>(crops_device);
+        int64_t* written = reinterpret_cast<int64_t*>(written_device);
+        // the launch shape comes from the binding alone: no crop is read here
+        if (b->fmt) {
+            DEC_TRY(gsc_launch_crop_resample_bound(b->streams.p, b->nstreams, crops, ncrops, length, C, is_float, planar,
+                                                   b->src_samples(std::min<int64_t>(length, kResampleTile)),
+                                                   dst_device, written, hs));
+        } else {
+            // a workgroup per 4 Ki samples of a crop, as gsc_decode_crops
+            DEC_TRY(gsc_launch_crop_fused_bound(b->streams.p, b->nstreams, crops, ncrops, length, C, is_float, planar,
+                                                int(std::min<int64_t>(length, 4096)), dst_device, written, hs));
+        }
+        ++stats.launches;
+    }
+    stats.host_ms = now_ms() - t_begin;
+    return 0;
+}
+
+void gsc_crop_binding_last_call(gsc_crop_call_stats* s) {
+    if (s) *s = t_bstat;
+}
+
+void gsc_crop_binding_free(gsc_crop_binding* b) {
+    if (!b) return;
+    int cur = 0;
+    const bool sw = hipGetDevice(&cur) == hipSuccess && cur != b->device;
+    if (sw) (void)hipSetDevice(b->device);
+    (void)hipDeviceSynchronize();  // queued calls still read the descriptors
+    delete b;
+    if (sw) (void)hipSetDevice(cur);
 }
 
 int gsc_stream_decode_samples(gsc_stream* st, long long begin, long long count, int16_t* pcm) {

@@ -19,6 +19,12 @@
 //   crop_synth_lds_kernel  a workgroup takes 16 Ki samples of one crop and
 //                       stages the codebook of every frame they cross in LDS,
 //                       as decode_synth_kernel does
+//   crop_fused_bound_kernel  crop_fused_kernel for gsc_crop_binding_decode,
+//                       whose crops live on the device: lane 0 of a workgroup
+//                       plans its crop from (stream, begin, count) and the
+//                       binding's stream descriptor (gsc_crop_plan.h), the
+//                       job goes through LDS to every wave's scalar registers,
+//                       and the rest is the same code
 // In all of them consecutive lanes write consecutive elements of the output
 // in either layout ([B][T][C] or [B][C][T]), so the stores coalesce, and
 // elements past a crop's clipped length are written as zero.
@@ -123,14 +129,10 @@ __global__ __launch_bounds__(kCropSynthThreads) void crop_synth_kernel(const Cro
 // share [ta, tb) with write(ua, ub, value), and puts its own barriers around
 // what it keeps in LDS.  What no frame of a stale span covers is zeroed too.
 template <typename T, bool PLANAR, int THREADS, typename Frame>
-__device__ __forceinline__ void crop_walk_tile(const CropJob* __restrict__ jobs, int ncrops, int64_t length,
-                                               int channels, int tile_len, int tiles, T* __restrict__ out,
-                                               int64_t nout, Frame frame) {
-    if (tiles <= 0 || channels <= 0 || tile_len <= 0) return;
-    const int64_t crop = blockIdx.x / tiles;
-    if (crop >= ncrops) return;
-    const CropJob& job = jobs[crop];
-    const int64_t t0 = (int64_t)(blockIdx.x - crop * tiles) * tile_len;
+__device__ __forceinline__ void crop_walk_job(const CropJob& job, int64_t crop, int64_t tile, int64_t length,
+                                              int channels, int tile_len, T* __restrict__ out, int64_t nout,
+                                              Frame frame) {
+    const int64_t t0 = tile * tile_len;
     const int64_t t1 = t0 + tile_len < length ? t0 + tile_len : length;
     if (t0 >= t1) return;
     const bool span_ok = job.f0 >= 0 && job.f0 < job.f1 && job.f1 <= job.nframes;
@@ -159,6 +161,18 @@ __device__ __forceinline__ void crop_walk_tile(const CropJob* __restrict__ jobs,
         done = tb;
     }
     write(done, tc, zero);
+}
+
+// crop_walk_job for the workgroup's tile of a call whose jobs the host planned
+template <typename T, bool PLANAR, int THREADS, typename Frame>
+__device__ __forceinline__ void crop_walk_tile(const CropJob* __restrict__ jobs, int ncrops, int64_t length,
+                                               int channels, int tile_len, int tiles, T* __restrict__ out,
+                                               int64_t nout, Frame frame) {
+    if (tiles <= 0 || channels <= 0 || tile_len <= 0) return;
+    const int64_t crop = blockIdx.x / tiles;
+    if (crop >= ncrops) return;
+    crop_walk_job<T, PLANAR, THREADS>(jobs[crop], crop, blockIdx.x - crop * tiles, length, channels, tile_len, out,
+                                      nout, frame);
 }
 
 // A workgroup: a run of tile_len samples of one crop.  Each frame's codebook
@@ -200,47 +214,71 @@ __global__ __launch_bounds__(kDecodeSynthThreads) void crop_synth_lds_kernel(
 constexpr int kFusedThreads = 256;
 constexpr int kFusedSegs = 64;
 
+// crop_walk_job's `frame` of the fused kernels: ssym holds kFusedSegs segments, slut 32 words
+__device__ __forceinline__ auto fused_frame(uint16_t* ssym, int* slut, int tid) {
+    return [=](const CropJob& job, const ResFrame& f, int, int64_t ta, int64_t tb, auto write) {
+        const int cs = f.cs, ch = f.ch;
+        const TableSlabs g = crop_tables(job);
+        const int64_t off = job.begin - f.first_sample;  // sample of the frame = off + t
+        const int64_t qa = (off + ta) / cs, qb = (off + tb - 1) / cs;
+        // rows per stretch: their symbols span at most kFusedSegs segments wherever the stretch starts
+        const int64_t rows = (int64_t)(kFusedSegs - 1) * kDecodeS / ch;
+        for (int64_t q0 = qa; q0 <= qb; q0 += rows) {
+            const int64_t q1 = q0 + rows - 1 < qb ? q0 + rows - 1 : qb;
+            const int64_t seg_lo = q0 * ch / kDecodeS;
+            int64_t nseg = ((q1 + 1) * ch - 1) / kDecodeS - seg_lo + 1;
+            nseg = nseg > kFusedSegs ? kFusedSegs : nseg;
+            __syncthreads();  // the previous stretch's symbols are no longer read
+            if (tid < 32) slut[tid] = f.lut[tid];
+            for (int i = tid; i < (int)nseg; i += kFusedThreads) {
+                uint16_t* o = ssym + i * kDecodeS;
+                if (!crop_unpack_one(job, f, seg_lo + i, o))
+                    for (int z = 0; z < kDecodeS; ++z) o[z] = 0;
+            }
+            __syncthreads();
+            int64_t ua = q0 * cs - off, ub = (q1 + 1) * cs - off;
+            ua = ua < ta ? ta : ua;
+            ub = ub > tb ? tb : ub;
+            write(ua, ub, [&](int64_t t, int k) {
+                const int64_t local = off + t;
+                const int64_t rel = local / cs * ch + k - seg_lo * kDecodeS;  // the symbol's place in ssym
+                if (k < ch && local >= 0 && rel >= 0 && rel < nseg * kDecodeS && local / cs * ch + k < f.nsym)
+                    return table_sample(f, slut, ssym[rel], (int)(local % cs), StagedTables{}, g);
+                return (int16_t)0;
+            });
+        }
+    };
+}
+
 template <typename T, bool PLANAR>
 __global__ __launch_bounds__(kFusedThreads) void crop_fused_kernel(const CropJob* __restrict__ jobs, int ncrops,
                                                                    int64_t length, int channels, int tile_len,
                                                                    int tiles, T* __restrict__ out, int64_t nout) {
     __shared__ uint16_t ssym[kFusedSegs * kDecodeS];
     __shared__ int slut[32];
-    const int tid = threadIdx.x;
-    crop_walk_tile<T, PLANAR, kFusedThreads>(
-        jobs, ncrops, length, channels, tile_len, tiles, out, nout,
-        [&](const CropJob& job, const ResFrame& f, int, int64_t ta, int64_t tb, auto write) {
-            const int cs = f.cs, ch = f.ch;
-            const TableSlabs g = crop_tables(job);
-            const int64_t off = job.begin - f.first_sample;  // sample of the frame = off + t
-            const int64_t qa = (off + ta) / cs, qb = (off + tb - 1) / cs;
-            // rows per stretch: their symbols span at most kFusedSegs segments wherever the stretch starts
-            const int64_t rows = (int64_t)(kFusedSegs - 1) * kDecodeS / ch;
-            for (int64_t q0 = qa; q0 <= qb; q0 += rows) {
-                const int64_t q1 = q0 + rows - 1 < qb ? q0 + rows - 1 : qb;
-                const int64_t seg_lo = q0 * ch / kDecodeS;
-                int64_t nseg = ((q1 + 1) * ch - 1) / kDecodeS - seg_lo + 1;
-                nseg = nseg > kFusedSegs ? kFusedSegs : nseg;
-                __syncthreads();  // the previous stretch's symbols are no longer read
-                if (tid < 32) slut[tid] = f.lut[tid];
-                for (int i = tid; i < (int)nseg; i += kFusedThreads) {
-                    uint16_t* o = ssym + i * kDecodeS;
-                    if (!crop_unpack_one(job, f, seg_lo + i, o))
-                        for (int z = 0; z < kDecodeS; ++z) o[z] = 0;
-                }
-                __syncthreads();
-                int64_t ua = q0 * cs - off, ub = (q1 + 1) * cs - off;
-                ua = ua < ta ? ta : ua;
-                ub = ub > tb ? tb : ub;
-                write(ua, ub, [&](int64_t t, int k) {
-                    const int64_t local = off + t;
-                    const int64_t rel = local / cs * ch + k - seg_lo * kDecodeS;  // the symbol's place in ssym
-                    if (k < ch && local >= 0 && rel >= 0 && rel < nseg * kDecodeS && local / cs * ch + k < f.nsym)
-                        return table_sample(f, slut, ssym[rel], (int)(local % cs), StagedTables{}, g);
-                    return (int16_t)0;
-                });
-            }
-        });
+    crop_walk_tile<T, PLANAR, kFusedThreads>(jobs, ncrops, length, channels, tile_len, tiles, out, nout,
+                                             fused_frame(ssym, slut, threadIdx.x));
+}
+
+// crop_fused_kernel for a bound call (gsc_crop_binding_decode): the workgroup
+// makes its crop's job itself from crops[crop] = (stream, begin, count) and the
+// binding's stream descriptors (bound_job), and the crop's first tile reports
+// written[crop].  A bad crop's row is zero over the whole length.
+template <typename T, bool PLANAR>
+__global__ __launch_bounds__(kFusedThreads) void crop_fused_bound_kernel(
+    const BoundStream* __restrict__ streams, int nstreams, const int64_t* __restrict__ crops, int ncrops,
+    int64_t length, int channels, int tile_len, int tiles, T* __restrict__ out, int64_t nout,
+    int64_t* __restrict__ written) {
+    __shared__ uint16_t ssym[kFusedSegs * kDecodeS];
+    __shared__ int slut[32];
+    __shared__ SharedJob sjob;
+    if (tiles <= 0 || channels <= 0 || tile_len <= 0 || nstreams <= 0) return;
+    const int64_t crop = blockIdx.x / tiles;
+    if (crop >= ncrops) return;
+    const int64_t tile = blockIdx.x - crop * tiles;
+    const CropJob job = bound_job(streams, nstreams, crops, crop, tile == 0, length, channels, written, &sjob);
+    crop_walk_job<T, PLANAR, kFusedThreads>(job, crop, tile, length, channels, tile_len, out, nout,
+                                            fused_frame(ssym, slut, threadIdx.x));
 }
 
 template <typename T, bool PLANAR>
@@ -280,10 +318,35 @@ hipError_t launch_fused(const CropJob* jobs, int ncrops, int64_t length, int cha
     return hipGetLastError();
 }
 
+template <typename T, bool PLANAR>
+hipError_t launch_fused_bound(const BoundStream* streams, int nstreams, const int64_t* crops, int ncrops,
+                              int64_t length, int channels, int tile_len, void* out, int64_t* written,
+                              hipStream_t st) {
+    if (tile_len <= 0 || tile_len > (1 << 20) || channels > 255) return hipErrorInvalidValue;
+    const int64_t tiles = (length + tile_len - 1) / tile_len;
+    if (tiles * ncrops > 0x7fffffff) return hipErrorInvalidValue;
+    hipLaunchKernelGGL((crop_fused_bound_kernel<T, PLANAR>), dim3((unsigned)(tiles * ncrops)), dim3(kFusedThreads), 0,
+                       st, streams, nstreams, crops, ncrops, length, channels, tile_len, (int)tiles,
+                       static_cast<T*>(out), (int64_t)ncrops * length * channels, written);
+    return hipGetLastError();
+}
+
 }  // namespace
 }  // namespace gsc
 
 using namespace gsc;
+
+// gsc_launch_crop_fused for a bound call: crops is [ncrops][3] on the device,
+// written [ncrops] there or null
+extern "C" hipError_t gsc_launch_crop_fused_bound(const BoundStream* streams, int nstreams, const int64_t* crops,
+                                                  int ncrops, int64_t length, int channels, int is_float, int planar,
+                                                  int tile_len, void* out, int64_t* written, hipStream_t st) {
+    if (ncrops <= 0 || length <= 0 || channels <= 0 || nstreams <= 0) return hipSuccess;
+    return dispatch_out(is_float, planar, [&](auto t, auto p) {
+        return launch_fused_bound<decltype(t), decltype(p)::value>(streams, nstreams, crops, ncrops, length, channels,
+                                                                   tile_len, out, written, st);
+    });
+}
 
 extern "C" hipError_t gsc_launch_crop_unpack(const CropJob* jobs, int ncrops, const CropPiece* pieces, int npieces,
                                              uint16_t* sym, int64_t nslots, hipStream_t st) {

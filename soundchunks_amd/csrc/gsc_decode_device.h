@@ -3,7 +3,8 @@
 // walk of one checkpoint segment and the sample arithmetic
 // (decoder/decoder.lpr:163-203), the binary search, a frame's tables staged in
 // LDS or read from global memory, a crop's segments, frames and output
-// elements, and the dynamic-LDS limit.
+// elements, the job of a crop that is planned on the device, and the
+// dynamic-LDS limit.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -11,6 +12,7 @@
 #include <atomic>
 #include <type_traits>
 
+#include "gsc_crop_plan.h"
 #include "gsc_decode.h"
 
 namespace gsc {
@@ -231,6 +233,97 @@ __device__ __forceinline__ void crop_write_run(int64_t ta, int64_t tb, int chann
         const int64_t oi = crop_elem<PLANAR>(l, nt, ta, channels, length, out_base, &t, &k);
         if (oi >= 0 && oi < nout) out[oi] = to_out<T>(value(t, k));
     }
+}
+
+// ---- crops whose list lives on the device (gsc_crop_binding_decode) ----
+
+// A value every lane of the wave holds alike, in scalar registers from here on.
+__device__ __forceinline__ int32_t wave_uniform(int32_t v) { return __builtin_amdgcn_readfirstlane(v); }
+__device__ __forceinline__ int64_t wave_uniform(int64_t v) {
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(uint64_t)v);
+    const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)((uint64_t)v >> 32));
+    return (int64_t)((uint64_t)hi << 32 | lo);
+}
+template <typename P>
+__device__ __forceinline__ const P* wave_uniform(const P* p) {
+    return reinterpret_cast<const P*>((uintptr_t)wave_uniform((int64_t)reinterpret_cast<uintptr_t>(p)));
+}
+
+// One lane: the CropJob of crop c = (stream, begin, count) of a bound call, as
+// plan_crops / plan_crops_fmt and the host fill it for the other calls.
+// Returns what the call reports as written: the clipped count, or -1 for a bad
+// crop, whose job is empty (f0 == f1), so that the kernels zero its row and
+// read nothing through it.  The stream index is checked before it is used, the
+// frame searches stay inside [0, nframes).
+__device__ __forceinline__ int64_t bound_plan(const BoundStream* __restrict__ streams, int nstreams,
+                                              const int64_t* __restrict__ c, int64_t length, int out_ch,
+                                              CropJob* job) {
+    CropJob j{};
+    int64_t written = -1;
+    const int64_t s = c[0], begin = c[1], count = c[2];
+    if (crop_stream_status(s, nstreams) == kCropGood) {
+        const BoundStream& d = streams[s];
+        const ResFrame* frames = d.frames;
+        CropSpan sp;
+        if (crop_plan_one(begin, count, length, d.samples, d.nframes, d.rate_up, d.rate_down, d.half_taps,
+                          [&](int i) { return frames[i].first_sample; }, &sp) == kCropGood) {
+            j = CropJob{frames,     d.cps,     d.words,  d.cb,      d.att, d.ncp, d.nwords,     d.ncb,
+                        d.natt,     begin,     sp.count, d.nframes, sp.f0, sp.f1, 0,            sp.src_begin,
+                        sp.src_end, d.table,   d.rate_up, d.rate_down, d.half_taps, d.channels, out_ch};
+            written = sp.count;
+        }
+    }
+    *job = j;
+    return written;
+}
+
+// bound_job's LDS: a whole number of 16 bytes, so that a kernel's static LDS
+// stays one and its dynamic LDS starts 16-byte aligned
+struct alignas(16) SharedJob {
+    CropJob job;
+};
+
+// Every lane of a workgroup, once, before anything else: the job of the
+// workgroup's crop.  Lane 0 alone reads the crop and runs the two frame
+// searches (bound_plan), leaves the job in *sjob (LDS) and, in the crop's first
+// tile, stores written[crop]; after the barrier every wave takes the job to
+// scalar registers, so that the rest of the kernel sees what a job loaded from
+// the host's array gives it.
+__device__ __forceinline__ CropJob bound_job(const BoundStream* __restrict__ streams, int nstreams,
+                                             const int64_t* __restrict__ crops, int64_t crop, bool first_tile,
+                                             int64_t length, int out_ch, int64_t* __restrict__ written,
+                                             SharedJob* shared) {
+    CropJob* sjob = &shared->job;
+    if (threadIdx.x == 0) {
+        const int64_t w = bound_plan(streams, nstreams, crops + 3 * crop, length, out_ch, sjob);
+        if (first_tile && written) written[crop] = w;
+    }
+    __syncthreads();
+    CropJob j;
+    j.frames = wave_uniform(sjob->frames);
+    j.cps = wave_uniform(sjob->cps);
+    j.words = wave_uniform(sjob->words);
+    j.cb = wave_uniform(sjob->cb);
+    j.att = wave_uniform(sjob->att);
+    j.ncp = wave_uniform(sjob->ncp);
+    j.nwords = wave_uniform(sjob->nwords);
+    j.ncb = wave_uniform(sjob->ncb);
+    j.natt = wave_uniform(sjob->natt);
+    j.begin = wave_uniform(sjob->begin);
+    j.count = wave_uniform(sjob->count);
+    j.nframes = wave_uniform(sjob->nframes);
+    j.f0 = wave_uniform(sjob->f0);
+    j.f1 = wave_uniform(sjob->f1);
+    j.piece0 = 0;
+    j.src_begin = wave_uniform(sjob->src_begin);
+    j.src_end = wave_uniform(sjob->src_end);
+    j.table = wave_uniform(sjob->table);
+    j.rate_up = wave_uniform(sjob->rate_up);
+    j.rate_down = wave_uniform(sjob->rate_down);
+    j.half_taps = wave_uniform(sjob->half_taps);
+    j.src_ch = wave_uniform(sjob->src_ch);
+    j.out_ch = wave_uniform(sjob->out_ch);
+    return j;
 }
 
 // f(T{}, std::bool_constant<PLANAR>{}) for the output's element type and layout

@@ -10,8 +10,9 @@ no CPU fallback for the decode itself; the index needs no GPU.
 ``Decoder.decode_crops`` then decodes batches of sample ranges of such streams
 straight into a torch tensor on the device, and ``decode_samples`` one range to
 numpy.  ``Decoder.open_many(gscs, tables)`` opens a whole corpus as one
-``StreamSet`` at a fixed number of runtime calls.  torch is imported by
-``decode_crops`` alone.
+``StreamSet`` at a fixed number of runtime calls.  ``Decoder.bind(streams)``
+describes streams once on the device (``CropBinding``), whose ``decode_crops``
+takes the crops from a device tensor.  torch is imported by the crop calls alone.
 """
 from __future__ import annotations
 
@@ -112,6 +113,21 @@ class Index:
         _lib.check(_lib.load().gsc_index_locate(self._h, int(sample), ctypes.byref(fr), ctypes.byref(row),
                                                 ctypes.byref(within), ctypes.byref(cp)))
         return fr.value, row.value, within.value, cp.value
+
+    def plan_crop(self, begin: int, count: int, length: int, rate=None, stream: int = 0, nstreams: int = 1) -> dict:
+        """What the kernels of a ``CropBinding`` make of crop (stream, begin,
+        count) of this stream (``gsc_crop_plan_model``; host only): ``status``
+        0 good, 1 / 2 / 3 a bad stream index / begin / count; ``written``, the
+        source range ``src_begin`` .. ``src_end`` and the frames ``f0`` .. ``f1``."""
+        w, sb, se = ctypes.c_longlong(0), ctypes.c_longlong(0), ctypes.c_longlong(0)
+        f0, f1 = ctypes.c_int(0), ctypes.c_int(0)
+        rc = _lib.load().gsc_crop_plan_model(self._h, int(nstreams), int(stream), int(begin), int(count), int(length),
+                                             0 if rate is None else int(rate), ctypes.byref(w), ctypes.byref(f0),
+                                             ctypes.byref(f1), ctypes.byref(sb), ctypes.byref(se))
+        if rc < 0:
+            _lib.check(rc)
+        return {"status": rc, "written": w.value, "f0": f0.value, "f1": f1.value, "src_begin": sb.value,
+                "src_end": se.value}
 
     def close(self) -> None:
         if getattr(self, "_h", None):
@@ -239,6 +255,10 @@ class StreamSet:
         return Decoder.decode_crops(self.streams, crops, length, dtype=dtype, layout=layout, out=out, rate=rate,
                                     channels=channels)
 
+    def bind(self, rate=None, channels=None):
+        """``Decoder.bind(self.streams, ...)``: crop stream indices count the set's members."""
+        return CropBinding(self.streams, rate=rate, channels=channels)
+
     def close(self) -> None:
         if getattr(self, "_h", None):
             for s in self._streams:
@@ -246,6 +266,120 @@ class StreamSet:
                     s.index.close()
                     s._h = None
             _lib.load().gsc_stream_set_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class CropBinding:
+    """The streams of a loader described once on the device
+    (``gsc_crop_binding``): ``decode_crops`` then takes ``(stream, begin,
+    count)`` from a device tensor and does nothing on the host but launch one
+    kernel, which plans every crop itself.  ``begin`` is in source samples of
+    the crop's stream; ``count`` and ``length`` are output samples at ``rate``.
+    The binding keeps its streams alive; once one of them, or its set, is
+    closed, ``decode_crops`` raises."""
+
+    def __init__(self, streams, rate=None, channels=None):
+        import torch
+
+        streams = list(streams)
+        if not streams:
+            raise _lib.GscError("bind: no streams")
+        if rate is not None and int(rate) <= 0:
+            raise _lib.GscError(f"bind: rate {rate} Hz: a rate must be positive")
+        if channels is not None and int(channels) <= 0:
+            raise _lib.GscError(f"bind: channels {channels}")
+        lib = _lib.load()
+        self._streams = streams
+        # what closes a stream: itself, or the set it belongs to
+        owners = {}
+        for s in streams:
+            o = s._set if getattr(s, "_set", None) is not None else s
+            owners[id(o)] = o
+        self._owners = list(owners.values())
+        self.channels = streams[0].channels if channels is None else int(channels)
+        self.rate = None if rate is None else int(rate)
+        self.device = torch.device("cuda", streams[0].device)
+        hs = (ctypes.c_void_p * len(streams))(*[s._handle() for s in streams])
+        with torch.cuda.device(self.device):
+            h = lib.gsc_crop_binding_create(hs, len(streams), 0 if rate is None else int(rate),
+                                            0 if channels is None else int(channels))
+        if not h:
+            raise _lib.GscError(lib.gsc_last_error().decode(errors="replace"))
+        self._h = h
+
+    def decode_crops(self, crops, length: int, dtype=None, layout: str = "TC", out=None, written=None):
+        """``crops``: a contiguous ``torch.int64`` tensor [B, 3] of (stream
+        index, begin, count) on the streams' device.  Returns ``(x, n)``: ``x``
+        as ``Decoder.decode_crops`` returns it, ``n`` a ``torch.int64`` tensor
+        [B] on the device with each crop's clipped length (``written`` if
+        given).  A bad crop (stream index, ``begin`` or ``count`` out of range)
+        gets an all-zero row and ``n[i] == -1``; the other rows do not notice.
+        The work is enqueued on torch's current stream; nothing is synchronised,
+        allocated or copied by the library, and no crop is read on the host."""
+        import torch
+
+        if not getattr(self, "_h", None):
+            raise _lib.GscError("the crop binding is closed")
+        for o in self._owners:
+            if not getattr(o, "_h", None):
+                raise _lib.GscError("a stream of the crop binding is closed")
+        device = self.device
+        if not isinstance(crops, torch.Tensor) or crops.device != device:
+            where = crops.device if isinstance(crops, torch.Tensor) else type(crops).__name__
+            raise _lib.GscError(f"bound decode_crops: crops must be a torch.int64 tensor [B, 3] on {device}, got "
+                                f"{where}; Decoder.decode_crops takes crops as a host list")
+        if crops.dtype != torch.int64 or crops.dim() != 2 or crops.shape[1] != 3 or not crops.is_contiguous():
+            raise _lib.GscError(f"bound decode_crops: crops must be a contiguous torch.int64 tensor [B, 3], got "
+                                f"{crops.dtype} {tuple(crops.shape)}; Decoder.decode_crops takes crops as a host list")
+        dtype = torch.int16 if dtype is None else dtype
+        if dtype not in (torch.int16, torch.float32):
+            raise _lib.GscError(f"bound decode_crops: dtype {dtype} is neither torch.int16 nor torch.float32")
+        if layout not in ("TC", "CT"):
+            raise _lib.GscError(f"bound decode_crops: layout {layout!r} is neither 'TC' nor 'CT'")
+        length = int(length)
+        if length < 0:
+            raise _lib.GscError(f"bound decode_crops: length {length}")
+        B, ch = crops.shape[0], self.channels
+        shape = (B, length, ch) if layout == "TC" else (B, ch, length)
+        if out is None:
+            out = torch.empty(shape, dtype=dtype, device=device)
+        else:
+            if out.device != device:
+                raise _lib.GscError(f"bound decode_crops: out is on {out.device}, the streams live on {device}")
+            if out.dtype != dtype or tuple(out.shape) != shape or not out.is_contiguous():
+                raise _lib.GscError(f"bound decode_crops: out must be a contiguous {dtype} tensor of shape {shape}, "
+                                    f"got {out.dtype} {tuple(out.shape)}")
+        if written is None:
+            # without a row to write the library launches nothing and reports nothing
+            written = (torch.empty if length else torch.zeros)((B,), dtype=torch.int64, device=device)
+        elif (written.device != device or written.dtype != torch.int64 or tuple(written.shape) != (B,) or
+              not written.is_contiguous()):
+            raise _lib.GscError(f"bound decode_crops: written must be a contiguous torch.int64 tensor [{B}] on "
+                                f"{device}")
+        pcm = _lib.PCM_FLOAT32 if dtype == torch.float32 else _lib.PCM_INT16
+        lay = _lib.LAYOUT_CT if layout == "CT" else _lib.LAYOUT_TC
+        with torch.cuda.device(device):
+            hip_stream = ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+            _lib.check(_lib.load().gsc_crop_binding_decode(self._h, crops.data_ptr(), B, pcm, lay, length,
+                                                           out.data_ptr(), written.data_ptr(), hip_stream))
+        return out, written
+
+    @staticmethod
+    def last_call() -> dict:
+        """The runtime calls of this thread's last ``decode_crops`` of a binding, and its host time."""
+        s = _lib.GscCropCallStats()
+        _lib.load().gsc_crop_binding_last_call(ctypes.byref(s))
+        return {k: getattr(s, k) for k, _ in s._fields_}
+
+    def close(self) -> None:
+        if getattr(self, "_h", None):
+            _lib.load().gsc_crop_binding_free(self._h)
             self._h = None
 
     def __del__(self):
@@ -403,6 +537,16 @@ class Decoder:
                 _lib.check(lib.gsc_decode_crops(hs, len(streams), cr, len(crops), pcm, lay, length, dst.data_ptr(),
                                                 hip_stream, written))
         return out, [int(written[i]) for i in range(len(crops))]
+
+    @staticmethod
+    def bind(streams, rate=None, channels=None) -> CropBinding:
+        """The streams described once on the device, for crop lists that live
+        there: ``bind(...).decode_crops(crops_tensor, length)`` is
+        ``decode_crops(streams, crops_list, length, rate=, channels=)`` without
+        the host plan, the allocation and the copy of each call.  ``rate`` and
+        ``channels`` as in ``decode_crops``; every resampler table is uploaded
+        here.  Refuses what ``decode_crops`` refuses of a stream, naming it."""
+        return CropBinding(streams, rate=rate, channels=channels)
 
     def decode(self, gsc: bytes, frame_begin: int = 0, frame_end: int = -1, table: bytes | None = None):
         """(int16 array [n, channels], sample_rate) of frames [frame_begin, frame_end).
