@@ -553,6 +553,45 @@ int gsc_crop_plan_model(const gsc_index *ix, int nstreams, int stream, long long
                         long long length, int out_rate, long long *written, int *f0, int *f1, long long *src_begin,
                         long long *src_end);
 
+/* ---- stream envelopes: block energy and peak of bound streams -------------------- */
+/* A sampler that draws crops on the device needs to know where a stream holds
+ * sound.  The envelope of a stream is computed straight from its resident
+ * compressed slabs by one kernel launch; no PCM is written to memory.
+ *
+ * Definition.  A stream has S samples per channel and C channels and decodes to
+ * int16 x[t][k], 0 <= t < S, 0 <= k < C, exactly as gsc_decode gives them.
+ * For a hop H, 64 <= H <= 65536 (any integer), the stream has nb = ceil(S / H)
+ * blocks; block b covers samples [b H, min((b + 1) H, S)) of every channel:
+ *   energy[b] = sum of x[t][k]^2 over the block's samples and all channels, as
+ *               int64 (it does not fit 32 bits);
+ *   peak[b]   = max of |x[t][k]| over the same, as int32, so that |-32768| =
+ *               32768 is representable.
+ * The last block is partial when H does not divide S; S = 0 gives no blocks.
+ * Blocks count source samples of the stream: a binding's out_rate and
+ * out_channels play no part, which is the unit of a crop's `begin`.  For
+ * several streams the blocks are concatenated in the binding's order:
+ * offsets[i] is the first block of stream i, offsets[n] the total.  All of it
+ * is integer arithmetic, so the results do not depend on the order of the sums.
+ *
+ * gsc_envelope_layout: offsets[0 .. n] for n streams of samples[i] samples per
+ * channel.  Host only, no device needed.  Refused (-1 and gsc_last_error): hop
+ * outside [64, 65536], n < 0, a negative length (the stream named), and 2^31
+ * or more blocks in all.
+ *
+ * gsc_crop_binding_envelope: energy_device (int64) and peak_device (int32) are
+ * nblocks elements each in device memory; nblocks must equal the layout's
+ * total for the binding's streams.  Every block is written, zero where nothing
+ * decodes.  A once-per-corpus call like gsc_crop_binding_create: it may
+ * allocate, copy and block.  It uploads its own small layout with a blocking
+ * copy, launches one kernel on hip_stream and waits for that stream before it
+ * returns.  A total of 0 blocks launches nothing.  Refused: a null binding, a
+ * hop gsc_envelope_layout refuses, another nblocks, null outputs, outputs that
+ * are not device memory of the binding's device, and a calling thread bound to
+ * another device.  The streams must still be open. */
+int gsc_envelope_layout(const long long *samples, int n, int hop, long long *offsets);
+int gsc_crop_binding_envelope(gsc_crop_binding *b, int hop, long long *energy_device, int *peak_device,
+                              long long nblocks, void *hip_stream);
+
 /* Timing of the last gsc_decode*, gsc_stream_open or crop call on the calling
  * thread (milliseconds).  h2d_bytes: the bytes that call uploaded. */
 typedef struct {

@@ -236,6 +236,9 @@ SIGNATURES = {
                                                ctypes.c_void_p]),
     "gsc_crop_binding_last_call": (None, [ctypes.POINTER(GscCropCallStats)]),
     "gsc_crop_binding_free": (None, [ctypes.c_void_p]),
+    "gsc_envelope_layout": (ctypes.c_int, [_LLP, ctypes.c_int, ctypes.c_int, _LLP]),
+    "gsc_crop_binding_envelope": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
+                                                 ctypes.c_longlong, ctypes.c_void_p]),
     "gsc_crop_plan_model": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_longlong,
                                            ctypes.c_longlong, ctypes.c_longlong, ctypes.c_int, _LLP, _IP, _IP, _LLP,
                                            _LLP]),

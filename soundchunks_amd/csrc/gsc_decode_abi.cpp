@@ -27,6 +27,7 @@
 #include "gsc_crop_plan.h"
 #include "gsc_decode.h"
 #include "gsc_device.h"
+#include "gsc_envelope.h"
 
 extern "C" hipError_t gsc_launch_decode_unpack(const gsc::DecFrame* frames, int nframes, const uint64_t* cps,
                                                int64_t ncp, const uint32_t* words, int64_t nwords, uint16_t* sym,
@@ -64,6 +65,9 @@ extern "C" hipError_t gsc_launch_crop_resample_bound(const gsc::BoundStream* str
                                                      int is_float, int planar, int src_samples, void* out,
                                                      int64_t* written, hipStream_t st);
 extern "C" hipError_t gsc_prepare_crop_resample_bound(int src_samples);
+extern "C" hipError_t gsc_launch_envelope(const gsc::BoundStream* streams, int nstreams, const int64_t* layout,
+                                          int64_t ntiles, int hop, int64_t* energy, int32_t* peak, int64_t nblocks,
+                                          hipStream_t st);
 
 struct gsc_index {
     gsc::Index ix;
@@ -400,6 +404,7 @@ struct gsc_crop_binding {
     int max_step = 1;      // the largest rate_down: bounds `length`
     gsc::Dev<gsc::BoundStream> streams;
     std::vector<gsc::BoundShape> shapes;  // the distinct ones of the streams
+    std::vector<int64_t> samples;         // per stream, per channel: the blocks of an envelope
 
     // The int16 source samples a workgroup of the resampling kernel keeps for a tile of `tile`
     // outputs: the widest source span over the binding's streams, all channels (as gsc_decode_crops_fmt
@@ -1163,6 +1168,7 @@ gsc_crop_binding* gsc_crop_binding_create(gsc_stream* const* streams, int nstrea
                                       table,     int32_t(ix.frames.size()), cs,       sh.phases,
                                       sh.step,   sh.half_taps, 0};
         b->max_step = std::max(b->max_step, sh.step);
+        b->samples.push_back(ix.samples);
         const BoundShape shape{sh.phases, sh.step, sh.half_taps, cs};
         if (std::find(b->shapes.begin(), b->shapes.end(), shape) == b->shapes.end()) b->shapes.push_back(shape);
     }
@@ -1221,6 +1227,61 @@ int gsc_crop_binding_decode(gsc_crop_binding* b, const long long* crops_device, 
 
 void gsc_crop_binding_last_call(gsc_crop_call_stats* s) {
     if (s) *s = t_bstat;
+}
+
+int gsc_envelope_layout(const long long* samples, int n, int hop, long long* offsets) {
+    static_assert(sizeof(long long) == sizeof(int64_t), "the layout is int64");
+    std::string err;
+    if (envelope_layout(reinterpret_cast<const int64_t*>(samples), n, hop, reinterpret_cast<int64_t*>(offsets), nullptr,
+                        &err) != 0)
+        return set_last_error(err);
+    return 0;
+}
+
+int gsc_crop_binding_envelope(gsc_crop_binding* b, int hop, long long* energy_device, int* peak_device,
+                              long long nblocks, void* hip_stream) {
+    if (!b) return set_last_error("gsc_crop_binding_envelope: binding is null");
+    const int n = b->nstreams;
+    // tile0[n + 1], then block0[n + 1], as envelope_kernel reads them
+    std::vector<int64_t> layout(2 * (size_t(n) + 1));
+    int64_t* tile0 = layout.data();
+    int64_t* block0 = tile0 + n + 1;
+    std::string err;
+    if (envelope_layout(b->samples.data(), n, hop, block0, tile0, &err) != 0) return set_last_error(err);
+    if (nblocks != block0[n])
+        return set_last_error("gsc_crop_binding_envelope: nblocks " + std::to_string(nblocks) + ", the binding's " +
+                              std::to_string(n) + " streams have " + std::to_string(block0[n]) + " blocks of " +
+                              std::to_string(hop) + " samples");
+    if (n == 0 || nblocks == 0) return 0;
+    if (!energy_device) return set_last_error("gsc_crop_binding_envelope: energy_device is null");
+    if (!peak_device) return set_last_error("gsc_crop_binding_envelope: peak_device is null");
+    int dev = 0;
+    DEC_TRY(hipGetDevice(&dev));
+    if (dev != b->device)
+        return set_last_error("gsc_crop_binding_envelope: the binding lives on device " + std::to_string(b->device) +
+                              ", the calling thread is bound to device " + std::to_string(dev));
+    // once per corpus: the call may ask the runtime where its outputs live
+    const std::pair<const void*, const char*> outs[2] = {{energy_device, "energy_device"}, {peak_device, "peak_device"}};
+    for (const auto& o : outs) {
+        hipPointerAttribute_t at{};
+        const hipError_t e = hipPointerGetAttributes(&at, o.first);
+        if (e != hipSuccess) (void)hipGetLastError();
+        if (e != hipSuccess || (at.type != hipMemoryTypeDevice && at.type != hipMemoryTypeManaged))
+            return set_last_error(std::string("gsc_crop_binding_envelope: ") + o.second + " is not device memory");
+        if (at.type == hipMemoryTypeDevice && at.device != b->device)
+            return set_last_error(std::string("gsc_crop_binding_envelope: ") + o.second + " lives on device " +
+                                  std::to_string(at.device) + ", the binding on device " + std::to_string(b->device));
+    }
+    hipStream_t hs = static_cast<hipStream_t>(hip_stream);
+    // The layout goes up as the binding's descriptors did: a blocking copy into memory of its own, which has
+    // landed when the call launches on whatever stream; the call then waits for that stream before it frees it.
+    Dev<int64_t> d_layout;
+    DEC_TRY(d_layout.alloc(layout.size()));
+    DEC_TRY(hipMemcpy(d_layout.p, layout.data(), layout.size() * sizeof(int64_t), hipMemcpyHostToDevice));
+    DEC_TRY(gsc_launch_envelope(b->streams.p, n, d_layout.p, tile0[n], hop, reinterpret_cast<int64_t*>(energy_device),
+                                peak_device, nblocks, hs));
+    DEC_TRY(hipStreamSynchronize(hs));
+    return 0;
 }
 
 void gsc_crop_binding_free(gsc_crop_binding* b) {

@@ -205,51 +205,7 @@ __global__ __launch_bounds__(kDecodeSynthThreads) void crop_synth_lds_kernel(
         });
 }
 
-// The fused variant: no symbol scratch and no unpack launch.  A workgroup
-// takes a run of tile_len samples of one crop; per frame the run crosses, and
-// per stretch of symbol rows whose symbols span at most kFusedSegs checkpoint
-// segments, its first lanes unpack those segments into LDS (one lane per
-// segment, as crop_unpack_kernel), then all lanes write the stretch's samples
-// with the codebook read from global memory.
-constexpr int kFusedThreads = 256;
-constexpr int kFusedSegs = 64;
-
-// crop_walk_job's `frame` of the fused kernels: ssym holds kFusedSegs segments, slut 32 words
-__device__ __forceinline__ auto fused_frame(uint16_t* ssym, int* slut, int tid) {
-    return [=](const CropJob& job, const ResFrame& f, int, int64_t ta, int64_t tb, auto write) {
-        const int cs = f.cs, ch = f.ch;
-        const TableSlabs g = crop_tables(job);
-        const int64_t off = job.begin - f.first_sample;  // sample of the frame = off + t
-        const int64_t qa = (off + ta) / cs, qb = (off + tb - 1) / cs;
-        // rows per stretch: their symbols span at most kFusedSegs segments wherever the stretch starts
-        const int64_t rows = (int64_t)(kFusedSegs - 1) * kDecodeS / ch;
-        for (int64_t q0 = qa; q0 <= qb; q0 += rows) {
-            const int64_t q1 = q0 + rows - 1 < qb ? q0 + rows - 1 : qb;
-            const int64_t seg_lo = q0 * ch / kDecodeS;
-            int64_t nseg = ((q1 + 1) * ch - 1) / kDecodeS - seg_lo + 1;
-            nseg = nseg > kFusedSegs ? kFusedSegs : nseg;
-            __syncthreads();  // the previous stretch's symbols are no longer read
-            if (tid < 32) slut[tid] = f.lut[tid];
-            for (int i = tid; i < (int)nseg; i += kFusedThreads) {
-                uint16_t* o = ssym + i * kDecodeS;
-                if (!crop_unpack_one(job, f, seg_lo + i, o))
-                    for (int z = 0; z < kDecodeS; ++z) o[z] = 0;
-            }
-            __syncthreads();
-            int64_t ua = q0 * cs - off, ub = (q1 + 1) * cs - off;
-            ua = ua < ta ? ta : ua;
-            ub = ub > tb ? tb : ub;
-            write(ua, ub, [&](int64_t t, int k) {
-                const int64_t local = off + t;
-                const int64_t rel = local / cs * ch + k - seg_lo * kDecodeS;  // the symbol's place in ssym
-                if (k < ch && local >= 0 && rel >= 0 && rel < nseg * kDecodeS && local / cs * ch + k < f.nsym)
-                    return table_sample(f, slut, ssym[rel], (int)(local % cs), StagedTables{}, g);
-                return (int16_t)0;
-            });
-        }
-    };
-}
-
+// The fused variant (fused_frame, gsc_decode_device.h): no symbol scratch and no unpack launch.
 template <typename T, bool PLANAR>
 __global__ __launch_bounds__(kFusedThreads) void crop_fused_kernel(const CropJob* __restrict__ jobs, int ncrops,
                                                                    int64_t length, int channels, int tile_len,

@@ -235,6 +235,53 @@ __device__ __forceinline__ void crop_write_run(int64_t ta, int64_t tb, int chann
     }
 }
 
+// ---- the fused walk of a frame (crop_fused_kernel, crop_fused_bound_kernel, envelope_kernel) ----
+
+// The fused variant: no symbol scratch and no unpack launch.  A workgroup
+// takes a run of tile_len samples of one crop; per frame the run crosses, and
+// per stretch of symbol rows whose symbols span at most kFusedSegs checkpoint
+// segments, its first lanes unpack those segments into LDS (one lane per
+// segment, as crop_unpack_kernel), then all lanes write the stretch's samples
+// with the codebook read from global memory.
+constexpr int kFusedThreads = 256;
+constexpr int kFusedSegs = 64;
+
+// crop_walk_job's `frame` of the fused kernels: ssym holds kFusedSegs segments, slut 32 words
+__device__ __forceinline__ auto fused_frame(uint16_t* ssym, int* slut, int tid) {
+    return [=](const CropJob& job, const ResFrame& f, int, int64_t ta, int64_t tb, auto write) {
+        const int cs = f.cs, ch = f.ch;
+        const TableSlabs g = crop_tables(job);
+        const int64_t off = job.begin - f.first_sample;  // sample of the frame = off + t
+        const int64_t qa = (off + ta) / cs, qb = (off + tb - 1) / cs;
+        // rows per stretch: their symbols span at most kFusedSegs segments wherever the stretch starts
+        const int64_t rows = (int64_t)(kFusedSegs - 1) * kDecodeS / ch;
+        for (int64_t q0 = qa; q0 <= qb; q0 += rows) {
+            const int64_t q1 = q0 + rows - 1 < qb ? q0 + rows - 1 : qb;
+            const int64_t seg_lo = q0 * ch / kDecodeS;
+            int64_t nseg = ((q1 + 1) * ch - 1) / kDecodeS - seg_lo + 1;
+            nseg = nseg > kFusedSegs ? kFusedSegs : nseg;
+            __syncthreads();  // the previous stretch's symbols are no longer read
+            if (tid < 32) slut[tid] = f.lut[tid];
+            for (int i = tid; i < (int)nseg; i += kFusedThreads) {
+                uint16_t* o = ssym + i * kDecodeS;
+                if (!crop_unpack_one(job, f, seg_lo + i, o))
+                    for (int z = 0; z < kDecodeS; ++z) o[z] = 0;
+            }
+            __syncthreads();
+            int64_t ua = q0 * cs - off, ub = (q1 + 1) * cs - off;
+            ua = ua < ta ? ta : ua;
+            ub = ub > tb ? tb : ub;
+            write(ua, ub, [&](int64_t t, int k) {
+                const int64_t local = off + t;
+                const int64_t rel = local / cs * ch + k - seg_lo * kDecodeS;  // the symbol's place in ssym
+                if (k < ch && local >= 0 && rel >= 0 && rel < nseg * kDecodeS && local / cs * ch + k < f.nsym)
+                    return table_sample(f, slut, ssym[rel], (int)(local % cs), StagedTables{}, g);
+                return (int16_t)0;
+            });
+        }
+    };
+}
+
 // ---- crops whose list lives on the device (gsc_crop_binding_decode) ----
 
 // A value every lane of the wave holds alike, in scalar registers from here on.
@@ -283,22 +330,9 @@ struct alignas(16) SharedJob {
     CropJob job;
 };
 
-// Every lane of a workgroup, once, before anything else: the job of the
-// workgroup's crop.  Lane 0 alone reads the crop and runs the two frame
-// searches (bound_plan), leaves the job in *sjob (LDS) and, in the crop's first
-// tile, stores written[crop]; after the barrier every wave takes the job to
-// scalar registers, so that the rest of the kernel sees what a job loaded from
-// the host's array gives it.
-__device__ __forceinline__ CropJob bound_job(const BoundStream* __restrict__ streams, int nstreams,
-                                             const int64_t* __restrict__ crops, int64_t crop, bool first_tile,
-                                             int64_t length, int out_ch, int64_t* __restrict__ written,
-                                             SharedJob* shared) {
-    CropJob* sjob = &shared->job;
-    if (threadIdx.x == 0) {
-        const int64_t w = bound_plan(streams, nstreams, crops + 3 * crop, length, out_ch, sjob);
-        if (first_tile && written) written[crop] = w;
-    }
-    __syncthreads();
+// A job that one lane left in LDS, to every wave's scalar registers (after the barrier that
+// follows the store).
+__device__ __forceinline__ CropJob shared_job_load(const CropJob* sjob) {
     CropJob j;
     j.frames = wave_uniform(sjob->frames);
     j.cps = wave_uniform(sjob->cps);
@@ -324,6 +358,25 @@ __device__ __forceinline__ CropJob bound_job(const BoundStream* __restrict__ str
     j.src_ch = wave_uniform(sjob->src_ch);
     j.out_ch = wave_uniform(sjob->out_ch);
     return j;
+}
+
+// Every lane of a workgroup, once, before anything else: the job of the
+// workgroup's crop.  Lane 0 alone reads the crop and runs the two frame
+// searches (bound_plan), leaves the job in *sjob (LDS) and, in the crop's first
+// tile, stores written[crop]; after the barrier every wave takes the job to
+// scalar registers, so that the rest of the kernel sees what a job loaded from
+// the host's array gives it.
+__device__ __forceinline__ CropJob bound_job(const BoundStream* __restrict__ streams, int nstreams,
+                                             const int64_t* __restrict__ crops, int64_t crop, bool first_tile,
+                                             int64_t length, int out_ch, int64_t* __restrict__ written,
+                                             SharedJob* shared) {
+    CropJob* sjob = &shared->job;
+    if (threadIdx.x == 0) {
+        const int64_t w = bound_plan(streams, nstreams, crops + 3 * crop, length, out_ch, sjob);
+        if (first_tile && written) written[crop] = w;
+    }
+    __syncthreads();
+    return shared_job_load(sjob);
 }
 
 // f(T{}, std::bool_constant<PLANAR>{}) for the output's element type and layout

@@ -12,7 +12,10 @@ straight into a torch tensor on the device, and ``decode_samples`` one range to
 numpy.  ``Decoder.open_many(gscs, tables)`` opens a whole corpus as one
 ``StreamSet`` at a fixed number of runtime calls.  ``Decoder.bind(streams)``
 describes streams once on the device (``CropBinding``), whose ``decode_crops``
-takes the crops from a device tensor.  torch is imported by the crop calls alone.
+takes the crops from a device tensor, and whose ``envelope`` gives the block
+energy and peak of every bound stream (``Envelope``), from which
+``Envelope.sample_crops`` draws crops where there is sound.  torch is imported
+by the crop and envelope calls alone.
 """
 from __future__ import annotations
 
@@ -179,6 +182,10 @@ class ResidentStream:
                                                          out.ctypes.data_as(ctypes.POINTER(ctypes.c_int16))))
         return out
 
+    def envelope(self, hop: int = 1024) -> "Envelope":
+        """``Decoder.envelope([self], hop)``."""
+        return Decoder.envelope([self], hop)
+
     def _handle(self):
         if not getattr(self, "_h", None):
             raise _lib.GscError("the resident stream is closed")
@@ -258,6 +265,10 @@ class StreamSet:
     def bind(self, rate=None, channels=None):
         """``Decoder.bind(self.streams, ...)``: crop stream indices count the set's members."""
         return CropBinding(self.streams, rate=rate, channels=channels)
+
+    def envelope(self, hop: int = 1024) -> "Envelope":
+        """``Decoder.envelope(self.streams, hop)``: stream indices count the set's members."""
+        return Decoder.envelope(self.streams, hop)
 
     def close(self) -> None:
         if getattr(self, "_h", None):
@@ -370,6 +381,48 @@ class CropBinding:
                                                            out.data_ptr(), written.data_ptr(), hip_stream))
         return out, written
 
+    def envelope(self, hop: int = 1024, energy=None, peak=None) -> "Envelope":
+        """Block energy and peak of every bound stream (include/soundchunks.h
+        has the definition): per block of ``hop`` source samples (64 ..
+        65536) of a stream, all channels, the sum of squares as ``torch.int64``
+        and the largest magnitude as ``torch.int32``, the streams' blocks back
+        to back in the binding's order.  One kernel launch on torch's current
+        stream, straight from the compressed slabs; the binding's ``rate`` and
+        ``channels`` play no part.  A once-per-corpus call: it allocates,
+        copies its layout and waits for the stream.  ``energy`` / ``peak``:
+        contiguous tensors of the layout's total on the streams' device to
+        write into."""
+        import torch
+
+        if not getattr(self, "_h", None):
+            raise _lib.GscError("the crop binding is closed")
+        for o in self._owners:
+            if not getattr(o, "_h", None):
+                raise _lib.GscError("a stream of the crop binding is closed")
+        device = self.device
+        hop = int(hop)
+        samples = [int(s.samples_per_channel) for s in self._streams]
+        channels = [int(s.channels) for s in self._streams]
+        offsets = Decoder.envelope_layout(samples, hop)
+        total = offsets[-1]
+        made = []
+        for name, t, dt in (("energy", energy, torch.int64), ("peak", peak, torch.int32)):
+            if t is None:
+                t = torch.empty((total,), dtype=dt, device=device)
+            elif not isinstance(t, torch.Tensor) or t.device != device:
+                where = t.device if isinstance(t, torch.Tensor) else type(t).__name__
+                raise _lib.GscError(f"envelope: {name} must be a tensor on {device}, got {where}")
+            elif t.dtype != dt or tuple(t.shape) != (total,) or not t.is_contiguous():
+                raise _lib.GscError(f"envelope: {name} must be a contiguous {dt} tensor [{total}], got {t.dtype} "
+                                    f"{tuple(t.shape)}")
+            made.append(t)
+        energy, peak = made
+        with torch.cuda.device(device):
+            hip_stream = ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+            _lib.check(_lib.load().gsc_crop_binding_envelope(self._h, hop, energy.data_ptr(), peak.data_ptr(), total,
+                                                             hip_stream))
+        return Envelope(hop, samples, channels, offsets, energy, peak)
+
     @staticmethod
     def last_call() -> dict:
         """The runtime calls of this thread's last ``decode_crops`` of a binding, and its host time."""
@@ -387,6 +440,106 @@ class CropBinding:
             self.close()
         except Exception:
             pass
+
+
+class Envelope:
+    """Block energy and peak of the streams of a binding
+    (``CropBinding.envelope``).  ``hop``; ``samples`` and ``channels`` per stream
+    (host lists); ``offsets``: ``torch.int64`` [n + 1] on the device, stream i's
+    first block, and ``offsets_host``, the same as a list; ``energy``
+    ``torch.int64`` [total] and ``peak`` ``torch.int32`` [total] on the device.
+    It owns plain tensors, so it outlives the binding and the streams."""
+
+    def __init__(self, hop, samples, channels, offsets_host, energy, peak):
+        import torch
+
+        self.hop = int(hop)
+        self.samples, self.channels = list(samples), list(channels)
+        self.offsets_host = list(offsets_host)
+        self.energy, self.peak = energy, peak
+        device = energy.device
+        i64 = dict(dtype=torch.int64, device=device)
+        self.offsets = torch.tensor(self.offsets_host, **i64)
+        self._samples = torch.tensor(self.samples, **i64).reshape(-1)
+        total = self.offsets_host[-1]
+        # per block: its stream, its first sample and its samples (the last block of a stream is partial)
+        b = torch.arange(total, **i64)
+        self._stream = torch.searchsorted(self.offsets[1:].contiguous(), b, right=True)
+        self._first = (b - self.offsets[self._stream]) * self.hop
+        self._len = torch.clamp(self._samples[self._stream] - self._first, max=self.hop)
+        self._elems = self._len * torch.tensor(self.channels, **i64).reshape(-1)[self._stream]
+
+    def __len__(self) -> int:
+        return self.offsets_host[-1]
+
+    def blocks(self, i: int):
+        """(energy, peak) of stream i: views of its blocks."""
+        i = range(len(self.samples))[i]
+        a, b = self.offsets_host[i], self.offsets_host[i + 1]
+        return self.energy[a:b], self.peak[a:b]
+
+    def active(self, min_rms=None, min_peak=None):
+        """``torch.bool`` [total]: the blocks that hold sound.  ``min_rms`` (an
+        int, int16 units) is the exact integer test ``energy[b] >= min_rms**2 *
+        (samples in block b * channels of its stream)``; ``min_peak`` is
+        ``peak[b] >= min_peak``; both given: both must hold; neither: ``energy >
+        0``."""
+        if min_rms is None and min_peak is None:
+            return self.energy > 0
+        act = None
+        if min_rms is not None:
+            if int(min_rms) != min_rms or not 0 <= int(min_rms) <= 32768:
+                raise _lib.GscError(f"active: min_rms {min_rms!r} is not an int in [0, 32768]")
+            act = self.energy >= int(min_rms) ** 2 * self._elems  # at most 2^30 * 2^24
+        if min_peak is not None:
+            if int(min_peak) != min_peak:
+                raise _lib.GscError(f"active: min_peak {min_peak!r} is not an int")
+            p = self.peak >= int(min_peak)
+            act = p if act is None else act & p
+        return act
+
+    def sample_crops(self, n: int, span: int, count=None, min_rms=None, min_peak=None, generator=None):
+        """``torch.int64`` [n, 3] on the device for ``CropBinding.decode_crops``
+        of the same streams: n crops of ``span`` source samples, each around a
+        sample drawn uniformly from a uniformly drawn active block
+        (``active(min_rms, min_peak)``): ``begin = clamp(p - span // 2, 0,
+        max(samples - span, 0))``, so the crop holds p or is the whole stream.
+        Column 2 is ``count`` (default ``span``), the crop's length at the
+        binding's rate.  With no active block every row's stream is -1, which
+        the bound call reports as ``n[i] == -1`` and a zero row.  Device-side
+        ops on torch's current stream only: nothing is synchronised.
+        ``generator``: a ``torch.Generator`` of the envelope's device."""
+        import torch
+
+        n, span = int(n), int(span)
+        count = span if count is None else int(count)
+        if n < 0 or span < 1 or count < 0:
+            raise _lib.GscError(f"sample_crops: n {n}, span {span}, count {count}")
+        device = self.energy.device
+        i64 = dict(dtype=torch.int64, device=device)
+        total = len(self)
+        if total == 0 or n == 0:
+            out = torch.zeros((n, 3), **i64)
+            out[:, 0] = -1
+            out[:, 2] = count
+            return out
+        cum = torch.cumsum(self.active(min_rms, min_peak).to(torch.int64), 0)
+        active = cum[-1]  # stays on the device
+        u = torch.rand((2, n), dtype=torch.float64, device=device, generator=generator)
+        # the (r + 1)-th active block, r uniform in [0, active)
+        r = torch.minimum((u[0] * active).to(torch.int64), active - 1)
+        blk = torch.clamp(torch.searchsorted(cum, r, right=True), max=total - 1)
+        ln = self._len[blk]
+        p = self._first[blk] + torch.minimum((u[1] * ln).to(torch.int64), ln - 1)
+        stream = self._stream[blk]
+        last = torch.clamp(self._samples[stream] - span, min=0)
+        begin = torch.minimum(torch.clamp(p - span // 2, min=0), last)
+        some = active > 0
+        out = torch.empty((n, 3), **i64)
+        out[:, 0] = torch.where(some, stream, -1)
+        out[:, 1] = torch.where(some, begin, 0)
+        out[:, 2] = count
+        return out
 
 
 def wav_header(channels: int, rate: int, size: int) -> bytes:
@@ -547,6 +700,30 @@ class Decoder:
         ``channels`` as in ``decode_crops``; every resampler table is uploaded
         here.  Refuses what ``decode_crops`` refuses of a stream, naming it."""
         return CropBinding(streams, rate=rate, channels=channels)
+
+    @staticmethod
+    def envelope_layout(samples, hop: int):
+        """``offsets`` [n + 1] of an envelope of streams of ``samples[i]`` samples
+        per channel at ``hop``: stream i's first block, then the total
+        (``gsc_envelope_layout``).  Host only; raises for a hop outside 64 ..
+        65536, a negative length and 2**31 or more blocks."""
+        samples = [int(v) for v in samples]
+        n = len(samples)
+        arr = (ctypes.c_longlong * max(1, n))(*samples)
+        off = (ctypes.c_longlong * (n + 1))()
+        _lib.check(_lib.load().gsc_envelope_layout(arr, n, int(hop), off))
+        return [int(v) for v in off]
+
+    @staticmethod
+    def envelope(streams, hop: int = 1024) -> Envelope:
+        """The envelope of resident streams: binds them for the call
+        (``rate=None, channels=None``, so their channel counts must agree),
+        runs ``CropBinding.envelope`` and closes the binding again."""
+        b = CropBinding(streams)
+        try:
+            return b.envelope(hop)
+        finally:
+            b.close()
 
     def decode(self, gsc: bytes, frame_begin: int = 0, frame_end: int = -1, table: bytes | None = None):
         """(int16 array [n, channels], sample_rate) of frames [frame_begin, frame_end).
