@@ -20,17 +20,7 @@
 
 #include "../../include/soundchunks.h"
 #include "gsc_device.h"
-
-extern "C" hipError_t gsc_launch_yakmo(int D, const gsc::ReduceFrame* frames, int nframes, const float* X, float* C,
-                                       float* fs, int* is, float* gsum, uint32_t* gbits, int max_n, hipStream_t st);
-extern "C" size_t gsc_yakmo_big_floats(int64_t total_points, int nframes);
-extern "C" size_t gsc_yakmo_big_words(int64_t total_points, int nframes);
-extern "C" hipError_t gsc_launch_ann_build(const float* pts, int n, int dd, int* pidx, int* cd, float* cv, float* lo,
-                                           float* hi, float* bnd, float* val, hipStream_t st);
-extern "C" hipError_t gsc_launch_ann_query(const float* pts, int n, int dd, int* pidx, int* cd, float* cv, float* lo,
-                                           float* hi, float* bnd, const float* q, int k, int mode, float eps,
-                                           int* idxs, float* errs, float* dist, float* mk_key, int* mk_info,
-                                           float* pq_key, int* pq_h, int* pq_s, int* pq_n, hipStream_t st);
+#include "gsc_launch.h"
 
 namespace {
 

@@ -11,6 +11,7 @@
 #include <stdint.h>
 
 #include "gsc_device.h"
+#include "gsc_launch.h"
 
 namespace gsc {
 namespace ann {
@@ -440,7 +441,7 @@ __global__ __launch_bounds__(kOvBlock) void knnfit_ann_kernel(const Tree* __rest
             if ((double)box >= (double)mk.max_key()) break;  // box * (1 + eps)^2, eps = 0
             int h = nd.x, s = nd.y, n = nd.z;
             for (;;) {  // ANNkd_split::ann_pri_search: push the far child, descend the near one
-                // bounds check (the replay's arrays are poison-filled, gsc_runtime.cpp
+                // bounds check (the replay's arrays are poison-filled, gsc_encode_host.h
                 // DevArena): a node, segment or point index outside its tree's
                 // arrays reports -4 instead of reading another frame's memory
                 if (s < 0 || n < 1 || s + n > t.n || (t.ncap > 0 && (h < 0 || h >= t.ncap))) {

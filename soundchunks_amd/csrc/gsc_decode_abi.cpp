@@ -28,46 +28,8 @@
 #include "gsc_decode.h"
 #include "gsc_device.h"
 #include "gsc_envelope.h"
-
-extern "C" hipError_t gsc_launch_decode_unpack(const gsc::DecFrame* frames, int nframes, const uint64_t* cps,
-                                               int64_t ncp, const uint32_t* words, int64_t nwords, uint16_t* sym,
-                                               int64_t nsym, hipStream_t st);
-extern "C" hipError_t gsc_launch_decode_synth(const gsc::DecFrame* frames, int nframes, const gsc::DecJob* jobs,
-                                              int njobs, int lds_bytes, const uint16_t* sym, int64_t nsym,
-                                              const int16_t* cb, int64_t ncb, const uint8_t* att, int64_t natt,
-                                              int16_t* out, int64_t nout, hipStream_t st);
-
-extern "C" hipError_t gsc_launch_decode_verify(const gsc::ResFrame* frames, const uint64_t* frame_bits, int nframes,
-                                               const uint64_t* cps, int64_t ncp, const uint32_t* words, int64_t nwords,
-                                               unsigned long long* status, hipStream_t st, int* launched = nullptr);
-
-extern "C" hipError_t gsc_launch_expand_tables(const gsc::ResFrame* frames, const gsc::TableSrc* src, int nframes,
-                                               int64_t ncb_used, const uint8_t* bytes, int64_t nbytes, int16_t* cb,
-                                               int64_t ncb, uint8_t* att, int64_t natt, hipStream_t st,
-                                               int* launched);
-
-extern "C" hipError_t gsc_launch_crop_unpack(const gsc::CropJob* jobs, int ncrops, const gsc::CropPiece* pieces,
-                                             int npieces, uint16_t* sym, int64_t nslots, hipStream_t st);
-extern "C" hipError_t gsc_launch_crop_synth(const gsc::CropJob* jobs, int ncrops, const gsc::CropPiece* pieces,
-                                            int npieces, const uint16_t* sym, int64_t nslots, int64_t length,
-                                            int channels, int is_float, int planar, int lds_bytes, int tile_len,
-                                            void* out, hipStream_t st);
-extern "C" hipError_t gsc_launch_crop_fused(const gsc::CropJob* jobs, int ncrops, int64_t length, int channels,
-                                            int is_float, int planar, int tile_len, void* out, hipStream_t st);
-extern "C" hipError_t gsc_launch_crop_resample(const gsc::CropJob* jobs, int ncrops, int64_t length, int channels,
-                                               int is_float, int planar, int src_samples, void* out, hipStream_t st);
-
-extern "C" hipError_t gsc_launch_crop_fused_bound(const gsc::BoundStream* streams, int nstreams, const int64_t* crops,
-                                                  int ncrops, int64_t length, int channels, int is_float, int planar,
-                                                  int tile_len, void* out, int64_t* written, hipStream_t st);
-extern "C" hipError_t gsc_launch_crop_resample_bound(const gsc::BoundStream* streams, int nstreams,
-                                                     const int64_t* crops, int ncrops, int64_t length, int channels,
-                                                     int is_float, int planar, int src_samples, void* out,
-                                                     int64_t* written, hipStream_t st);
-extern "C" hipError_t gsc_prepare_crop_resample_bound(int src_samples);
-extern "C" hipError_t gsc_launch_envelope(const gsc::BoundStream* streams, int nstreams, const int64_t* layout,
-                                          int64_t ntiles, int hop, int64_t* energy, int32_t* peak, int64_t nblocks,
-                                          hipStream_t st);
+#include "gsc_hip_host.h"
+#include "gsc_launch.h"
 
 struct gsc_index {
     gsc::Index ix;
@@ -75,12 +37,6 @@ struct gsc_index {
 };
 
 namespace gsc {
-
-int set_last_error(const std::string& m);
-int require_device();
-// the host worker pool (gsc_runtime.cpp)
-void parallel_for(int n, int threads, const std::function<void(int)>& fn);
-int host_threads();
 
 namespace {
 
@@ -92,10 +48,6 @@ thread_local int* t_alloc_count = nullptr;
 // crop decode: 0 unpack, then synthesis with the codebook from global memory; 1 the same with the codebook
 // staged in LDS; 2 unpack and synthesis fused in one launch (DESIGN.md "f5 decoder" has the A/B)
 thread_local int t_crop_variant = 2;
-
-double now_ms() {
-    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
-}
 
 #define DEC_TRY(expr)                                                                                 \
     do {                                                                                              \
@@ -112,13 +64,6 @@ struct Dev {
     hipError_t alloc(size_t n) {
         if (t_alloc_count) ++*t_alloc_count;
         return hipMalloc(reinterpret_cast<void**>(&p), sizeof(T) * std::max<size_t>(n, 1));
-    }
-};
-
-struct Event {
-    hipEvent_t e = nullptr;
-    ~Event() {
-        if (e) (void)hipEventDestroy(e);
     }
 };
 
@@ -586,7 +531,7 @@ static int verify_resident(const Index& ix, const Slabs<ResFrame>& s) {
     DEC_TRY(hipMemcpy(d_bits.p, bits.data(), bits.size() * sizeof(uint64_t), hipMemcpyHostToDevice));
     DEC_TRY(hipMemcpy(d_status.p, &status, sizeof(status), hipMemcpyHostToDevice));
     DEC_TRY(gsc_launch_decode_verify(s.frames.p, d_bits.p, int(bits.size()), s.cps.p, s.ncp, s.words(), s.nwords,
-                                     d_status.p, nullptr));
+                                     d_status.p, nullptr, nullptr));
     DEC_TRY(hipMemcpy(&status, d_status.p, sizeof(status), hipMemcpyDeviceToHost));  // after the kernel
     return status == kVerifyOk ? 0 : set_last_error(verify_message(ix, status));
 }

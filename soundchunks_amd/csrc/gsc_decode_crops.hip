@@ -43,6 +43,7 @@
 
 #include "gsc_decode.h"
 #include "gsc_decode_device.h"
+#include "gsc_launch.h"
 
 namespace gsc {
 namespace {

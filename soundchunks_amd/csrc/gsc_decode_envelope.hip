@@ -38,6 +38,7 @@
 #include "gsc_decode.h"
 #include "gsc_decode_device.h"
 #include "gsc_envelope.h"
+#include "gsc_launch.h"
 
 namespace gsc {
 namespace {

@@ -1,5 +1,5 @@
 // SoundChunks MI355X encode hot path -- device-side descriptors shared by the
-// HIP kernels (gsc_kernels.hip) and the host runtime (gsc_runtime.cpp).
+// HIP kernels (gsc_kernels.hip) and the host stages (gsc_reduce_host.cpp and its siblings).
 //
 // All arrays live in HBM, one slab per batch of frames; a descriptor per frame
 // holds offsets into those slabs (no per-frame allocations).

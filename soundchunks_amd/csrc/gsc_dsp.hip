@@ -13,6 +13,7 @@
 
 #include "fpc_math.h"
 #include "gsc_device.h"
+#include "gsc_launch.h"
 
 namespace gsc {
 namespace {

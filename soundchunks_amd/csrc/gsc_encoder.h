@@ -88,8 +88,13 @@ struct ReconOut {
     double ms = 0;
 };
 
-// device slabs + stream of the KNNFit/packing pipeline of one encode (gsc_runtime.cpp)
+// device slabs + stream of the KNNFit/packing pipeline of one encode, and its
+// worker loop (gsc_encode_pipeline.cpp)
 struct PostCtx;
+struct PostLoop;
+// owner of a device buffer (gsc_hip_host.h)
+template <typename T>
+struct DevBuf;
 
 // -py reducer (gsc_birch_host.cpp): cluster.py's Birch labels of N samples
 int birch_reduce_labels(int n, int d, const float* feat, int K, int* labels, std::string* err);
@@ -142,8 +147,8 @@ class Encoder {
     // host side, features left in the device slab *dX at (*xoff)[i]; with dQ,
     // also the KNNFit queries Single(srcData) (N*CS floats per frame, frames
     // concatenated) in the device slab *dQ
-    int device_dsp(int b, std::vector<FrameState>& frames, void* dX, std::vector<int64_t>* xoff, double* ms,
-                   std::string* err, void* dQ = nullptr);
+    int device_dsp(int b, std::vector<FrameState>& frames, DevBuf<float>* dX, std::vector<int64_t>* xoff, double* ms,
+                   std::string* err, DevBuf<float>* dQ = nullptr);
     // reconstruction of frames [b, b + frames.size()) on the device (after KNNFit)
     int device_recon(int b, const std::vector<FrameState>& frames, ReconOut* ro, std::string* err);
     void frame_reduce_post(FrameState& f, bool reduced) const;
@@ -151,7 +156,8 @@ class Encoder {
     void frame_prune(FrameState& f, const int* use, int* remap) const;
     // SaveStream's header, attenuations and dstData (the index stream is packed on the device)
     void frame_save_head(FrameState& f) const;
-    // KNNFit, prune/sort and index packing of frames ids (gsc_runtime.cpp)
+    // KNNFit, prune/sort and index packing of frames ids (gsc_encode_pipeline.cpp)
+    friend struct PostLoop;
     int post_group(std::vector<FrameState>& frames, const std::vector<int>& ids, const std::vector<char>& reduced,
                    PostCtx& ctx, std::string* err);
 

@@ -17,6 +17,7 @@
 
 #include "gsc_device.h"
 #include "gsc_tree.h"
+#include "gsc_launch.h"
 
 namespace gsc {
 

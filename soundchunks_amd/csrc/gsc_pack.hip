@@ -24,6 +24,7 @@
 
 #include "gsc_decode.h"
 #include "gsc_device.h"
+#include "gsc_launch.h"
 
 namespace gsc {
 

@@ -18,6 +18,7 @@
 #include <stdint.h>
 
 #include "gsc_device.h"
+#include "gsc_launch.h"
 
 namespace gsc {
 namespace {

@@ -54,6 +54,7 @@
 // snapshot keeps the proof iff its live distance d_u > d(c*) and, when its
 // LCA with c* is a far step, d_u > B[lca]; a moved c* needs d(c*) < m2.
 #include "gsc_tree.h"
+#include "gsc_launch.h"
 
 namespace gsc {
 

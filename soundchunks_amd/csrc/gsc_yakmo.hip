@@ -25,6 +25,7 @@
 #include <stdint.h>
 
 #include "gsc_device.h"
+#include "gsc_launch.h"
 
 namespace gsc {
 namespace {

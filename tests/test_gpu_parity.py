@@ -84,7 +84,7 @@ def test_knnfit_overflow_replay_twice_per_stream(oracle):
     twice in one process on the null stream (the synchronous stage entry
     point) and twice on the encoder's non-blocking post-processing stream,
     interleaved.  Its device scratch is poison-filled before every replay
-    (gsc_runtime.cpp DevArena) and the replay kernel bounds-checks every node,
+    (gsc_encode_host.h DevArena) and the replay kernel bounds-checks every node,
     segment and point index, so a stale or uninitialised read shows up as a
     wrong answer or a -4 failure here instead of hiding behind zero pages."""
     import soundchunks_amd as sc
@@ -338,7 +338,7 @@ def test_python_reduce_file_matches_golden(name):
 def test_failed_encode_drains_before_next_encode():
     """An encode whose KNNFit/pack post-processing fails while its scan may
     still be running drains its stream and the device before the shared pinned
-    arena is released (gsc_runtime.cpp: lock, drain, PostCtx in that order), so
+    arena is released (gsc_encode_pipeline.cpp: lock, drain, PostCtx in that order), so
     a concurrent encode on another thread, which then takes the arena, is
     unaffected.  GSC_TEST_FAIL_POST fails exactly one post_group call."""
     import os
