@@ -274,14 +274,17 @@ enum { GSC_LAYOUT_TC = 0, GSC_LAYOUT_CT = 1 };    /* [B][T][C] interleaved, [B][
  * and the rest of the row up to `length` is zero.  Refused, with nothing
  * launched (<0 and gsc_last_error): begin < 0, begin > samples, count < 0,
  * count > length, a stream index outside [0, nstreams), streams whose channel
- * counts differ, a NULL dst_device, an unknown dtype or layout, and a stream
- * that lives on another device than the calling thread's.  Streams may differ
+ * counts differ, a NULL dst_device, an unknown dtype or layout, a stream of
+ * more than 2^40 samples per channel or a length of more than 2^40 (both "too
+ * long for one call", whatever the crops), and a stream that lives on another
+ * device than the calling thread's.  Streams may differ
  * in sample rate, ChunkSize and bit depth.  All crops run in one launch
  * (unpack of the checkpoint segments the crops touch and synthesis, fused),
  * enqueued on hip_stream (a hipStream_t; NULL: the default stream) and ordered
  * with it: the call contains no device synchronisation and copies no sample
- * to the host.  It uploads only its job descriptors; its scratch is allocated
- * and freed in stream order, so calls on different streams share nothing.
+ * to the host.  It uploads only its job descriptors and has no other scratch:
+ * that one block is allocated and freed in stream order, so calls on
+ * different streams share nothing.
  * The descriptors are uploaded with hipMemcpyAsync from pageable memory: the
  * runtime stages a copy that small (about 100 bytes per crop), but where it
  * cannot, HIP may complete the copy before returning, and the call then waits
@@ -293,13 +296,6 @@ int gsc_decode_crops(gsc_stream *const *streams, int nstreams, const gsc_crop *c
  * memory `pcm`, interleaved: the crop decode into device scratch and one
  * download.  The range must lie inside the stream. */
 int gsc_stream_decode_samples(gsc_stream *st, long long begin, long long count, int16_t *pcm);
-/* Measurement knob, per thread; NOT a stable part of the interface (it exists
- * for the A/B in DESIGN.md and may go once a size rule replaces it).  How
- * gsc_decode_crops runs: 0 unpack, then synthesis with the codebook read from
- * global memory; 1 the same with each frame's codebook staged in LDS; 2
- * unpack and synthesis fused in one launch (default).  Returns the previous
- * value; any other argument only queries.  The output does not depend on it. */
-int gsc_decode_crops_variant(int variant);
 
 /* ---- crops at a common sample rate and channel count -------------------------- */
 /* gsc_decode_crops with an output format: every row of the batch comes out at
@@ -593,7 +589,10 @@ int gsc_crop_binding_envelope(gsc_crop_binding *b, int hop, long long *energy_de
                               long long nblocks, void *hip_stream);
 
 /* Timing of the last gsc_decode*, gsc_stream_open or crop call on the calling
- * thread (milliseconds).  h2d_bytes: the bytes that call uploaded. */
+ * thread (milliseconds).  h2d_bytes: the bytes that call uploaded.  After
+ * gsc_decode_crops or gsc_decode_crops_fmt h2d_bytes is the job descriptors
+ * alone, frames the sum over the crops of the frames each one crosses, and
+ * symbols 0: the crop kernels unpack into LDS, no symbol scratch exists. */
 typedef struct {
     double host_index_ms, h2d_ms, gpu_unpack_ms, gpu_synth_ms, d2h_ms, total_ms;
     int frames;

@@ -247,7 +247,6 @@ SIGNATURES = {
     "gsc_resample_prepare": (ctypes.c_int, [ctypes.c_int, ctypes.c_int]),
     "gsc_resample_tile": (ctypes.c_int, []),
     "gsc_stream_decode_samples": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_longlong, ctypes.c_longlong, _I16P]),
-    "gsc_decode_crops_variant": (ctypes.c_int, [ctypes.c_int]),
     "gsc_decode_indexed": (ctypes.c_int, [_U8P, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
                                           ctypes.POINTER(_I16P), _SZP]),
     "gsc_decode": (ctypes.c_int, [_U8P, ctypes.c_size_t, ctypes.POINTER(_I16P), _SZP, _IP, _IP]),

@@ -1,10 +1,10 @@
-// The arithmetic of one crop, for the host and the device alike: what
-// plan_crops (gsc_decode_index.cpp) and plan_crops_fmt (gsc_resample.cpp) work
-// out per crop, as functions that compile with and without HIP.  The host
-// planners refuse a whole call for one bad crop; a crop list that lives on the
-// device (gsc_crop_binding) is planned by the decode kernels themselves with
-// these functions, and there a bad crop costs its own row only.
-// tools/decode/bound_check.cpp holds the two against each other.
+// The arithmetic of one crop, for the host and the device alike, as functions
+// that compile with and without HIP.  The host planner (plan_crops,
+// gsc_resample.cpp) calls crop_plan_one for every crop of a call and refuses
+// the whole call for one bad crop; a crop list that lives on the device
+// (gsc_crop_binding) is planned by the decode kernels themselves with the same
+// functions, and there a bad crop costs its own row only.
+// tools/decode/crop_check.cpp holds them against a model of its own.
 #pragma once
 #include <stdint.h>
 

@@ -203,8 +203,8 @@ int set_layout(const Index* const* ixs, int count, SetLayout* out, std::string* 
 int set_stream_of_checkpoint(const SetLayout& lay, int64_t c);
 
 // One crop on the device: its stream's slabs and their sizes, the clipped
-// sample range, the frames [f0, f1) it crosses and its first piece.
-// What follows piece0 is read by crop_resample_kernel alone (gsc_decode_resample.hip):
+// sample range and the frames [f0, f1) it crosses.
+// What follows f1 is read by crop_resample_kernel alone (gsc_decode_resample.hip):
 // there `begin` is in source samples, `count` in output samples, [f0, f1) are
 // the frames of the source range [src_begin, src_end) the filter reads inside
 // the stream, and rate_up / rate_down, half_taps and table are the resampler
@@ -217,7 +217,7 @@ struct CropJob {
     const uint8_t* att;
     int64_t ncp, nwords, ncb, natt;
     int64_t begin, count;
-    int32_t nframes, f0, f1, piece0;
+    int32_t nframes, f0, f1;
     int64_t src_begin, src_end;
     const int32_t* table;  // [rate_up][2 * half_taps] on the device
     int32_t rate_up, rate_down, half_taps;  // Fo / g, Fi / g, T
@@ -242,43 +242,28 @@ struct BoundStream {
     int32_t pad_;
 };
 
-// One frame of one crop: the checkpoint segments [seg0, seg0 + nseg) of the
-// frame are unpacked to segment slots [slot0, slot0 + nseg) of the call's
-// symbol scratch (kDecodeS words per slot).  A crop owns f1 - f0 pieces, one
-// per frame in order; an empty frame's piece has nseg 0.
-struct CropPiece {
-    int64_t slot0;
-    int64_t seg0;
-    int32_t nseg, crop, frame, pad_;
-};
-
 struct Crop {
     int stream;
     int64_t begin, count;
 };
 
-// The crops of one call, clipped and laid out (host only, no device needed).
+// The crops of one call, clipped (host only, no device needed; plan_crops below).
 struct PlanCrop {
     int stream;
-    int64_t begin, count;  // count clipped to the stream's end
-    int f0, f1, piece0;
-    // plan_crops_fmt: the source samples the crop reads inside its stream (the
-    // filter's reach on both sides of its outputs, clipped to [0, samples)), which
-    // [f0, f1) then cover, and the stream's resampler.  The phase of output 0 is
+    int64_t begin, count;  // count: output samples, clipped where the source position reaches the stream's end
+    // The source samples the crop reads inside its stream (the filter's reach on
+    // both sides of its outputs, clipped to [0, samples)), the frames [f0, f1)
+    // that hold them, and the stream's resampler.  The phase of output 0 is
     // (begin * rate_up) mod rate_up = 0 for every crop: `begin` is a whole sample.
+    // A crop that writes nothing (count 0) has all four spans 0 (crop_plan_one).
+    int f0 = 0, f1 = 0;
     int64_t src_begin = 0, src_end = 0;
     int rate_up = 1, rate_down = 1, half_taps = 0;
 };
 struct CropPlan {
     std::vector<PlanCrop> crops;
-    std::vector<CropPiece> pieces;
-    int64_t slots = 0;  // segment slots of the symbol scratch
     int channels = 0;
 };
-// Refuses (-1, *err) begin < 0, begin > samples, count < 0, count > length, a
-// bad stream index and streams whose channel counts differ.
-int plan_crops(const Index* const* ixs, int nstreams, const Crop* crops, int ncrops, int64_t length, CropPlan* plan,
-               std::string* err);
 
 // ---- crops at a common rate and channel count (gsc_decode_resample.hip) ------
 // The resampler of one pair of rates (include/soundchunks.h has the
@@ -304,14 +289,18 @@ const int32_t* resample_table(int in_rate, int out_rate, ResampleShape* shape, s
 // reaches `samples`: ceil((samples - begin) * phases / step).
 int64_t resample_outputs(int64_t samples, int64_t begin, const ResampleShape& s);
 
-// plan_crops for gsc_decode_crops_fmt: counts are output samples at out_rate
-// (0: every stream keeps its rate), clipped where the source position reaches
-// the stream's end.  out_channels 0: the streams must agree, as in plan_crops;
-// otherwise a stream must have out_channels channels or one, or out_channels is
-// one.  Also refused: a pair of rates resample_shape refuses, and a filter
-// whose reach times the stream's channels exceeds kResampleSrcCap.  No pieces:
-// the kernel unpacks what it needs itself.
-int plan_crops_fmt(const Index* const* ixs, int nstreams, const Crop* crops, int ncrops, int64_t length, int out_rate,
-                   int out_channels, CropPlan* plan, std::string* err);
+// The one host planner, of gsc_decode_crops (out_rate 0, out_channels 0) and
+// gsc_decode_crops_fmt: every crop through crop_plan_one (gsc_crop_plan.h), as
+// the kernels of a bound call plan theirs.  Counts are output samples at
+// out_rate (0: every stream keeps its rate), clipped where the source position
+// reaches the stream's end.  out_channels 0: the streams must agree; otherwise
+// a stream must have out_channels channels or one, or out_channels is one.
+// Refuses (-1, *err) a whole call for begin < 0, begin > samples, count < 0,
+// count > length or a bad stream index in any crop, a pair of rates
+// resample_shape refuses, a filter whose reach times the stream's channels
+// exceeds kResampleSrcCap, and a stream of more than 2^40 samples per channel
+// or a length of more than 2^40 / rate_down ("too long for one call").
+int plan_crops(const Index* const* ixs, int nstreams, const Crop* crops, int ncrops, int64_t length, int out_rate,
+               int out_channels, CropPlan* plan, std::string* err);
 
 }  // namespace gsc

@@ -5,7 +5,8 @@
 // gsc_decode.hip's two stages over all of them.  A resident stream
 // (gsc_stream_open, gsc_stream_open_with_table) keeps the index and the bytes on the
 // device; gsc_decode_crops then decodes batches of sample ranges into
-// caller-owned device memory (plan_crops; gsc_decode_crops.hip).  A stream set
+// caller-owned device memory (plan_crops; gsc_decode_crops.hip), gsc_decode_crops_fmt
+// at a common rate and channel count (gsc_decode_resample.hip).  A stream set
 // (gsc_stream_set_open) keeps many streams in one Slabs, laid out by
 // set_layout (gsc_decode_set.cpp), their tables expanded on the device.  All
 // keep their device copies in a Slabs and describe a frame with frame_tables.
@@ -45,9 +46,6 @@ thread_local gsc_open_timing t_otim;  // the last gsc_stream_open* / gsc_index_c
 thread_local gsc_set_open_timing t_stim;  // the last gsc_stream_set_open
 // where Dev::alloc counts its hipMalloc calls while a stream set opens (else null)
 thread_local int* t_alloc_count = nullptr;
-// crop decode: 0 unpack, then synthesis with the codebook from global memory; 1 the same with the codebook
-// staged in LDS; 2 unpack and synthesis fused in one launch (DESIGN.md "f5 decoder" has the A/B)
-thread_local int t_crop_variant = 2;
 
 #define DEC_TRY(expr)                                                                                 \
     do {                                                                                              \
@@ -283,6 +281,41 @@ int device_resample_table(int in_rate, int out_rate, const int32_t** table) {
     return 0;
 }
 
+// samples of a crop that one workgroup of the fused kernels takes: 8 or 9 segments of a stereo ChunkSize-8 stream
+constexpr int kCropTile = 4096;
+
+// The int16 source samples a workgroup of the resampling kernels keeps in LDS for a tile of `tile` outputs
+// of one stream, all channels.
+int64_t source_reach(int64_t tile, int rate_up, int rate_down, int half_taps, int channels) {
+    // rounded up, so that the kernel's outputs per pass come out as the whole tile
+    const int64_t reach = ((tile - 1) * rate_down + rate_up - 1) / rate_up + 2 * half_taps + 2;
+    return std::min<int64_t>(reach * channels, kResampleSrcCap);
+}
+
+// 0, or the refusal of an element type or layout no crop kernel writes
+int check_pcm_format(const char* who, int dtype, int layout) {
+    const bool dtype_ok = dtype == GSC_PCM_INT16 || dtype == GSC_PCM_FLOAT32;
+    if (dtype_ok && (layout == GSC_LAYOUT_TC || layout == GSC_LAYOUT_CT)) return 0;
+    return set_last_error(std::string(who) + (dtype_ok ? ": unknown layout" : ": unknown dtype"));
+}
+
+// the refusal of `what`, whose memory is device `lives`'s, on a thread bound to device `dev`
+std::string other_device(const std::string& what, int lives, int dev) {
+    return what + " lives on device " + std::to_string(lives) + ", the calling thread is bound to device " +
+           std::to_string(dev);
+}
+
+// delete h on its own device, after the work queued there: crop calls still read what h owns
+template <typename Handle>
+void free_on_device(Handle* h) {
+    int cur = 0;
+    const bool sw = hipGetDevice(&cur) == hipSuccess && cur != h->device;
+    if (sw) (void)hipSetDevice(h->device);
+    (void)hipDeviceSynchronize();
+    delete h;
+    if (sw) (void)hipSetDevice(cur);
+}
+
 }  // namespace
 }  // namespace gsc
 
@@ -292,7 +325,6 @@ int device_resample_table(int in_rate, int out_rate, const int32_t** table) {
 struct gsc_stream {
     gsc_index idx;
     int device = 0;
-    int lds_bytes = 0;  // the largest staged codebook + attenuations of a frame
     gsc::Slabs<gsc::ResFrame> slabs;  // its own; empty in a member of a set
     // what the kernels get: its own slabs, or the set's with `frames` at its own first frame
     const gsc::ResFrame* frames = nullptr;
@@ -351,16 +383,12 @@ struct gsc_crop_binding {
     std::vector<gsc::BoundShape> shapes;  // the distinct ones of the streams
     std::vector<int64_t> samples;         // per stream, per channel: the blocks of an envelope
 
-    // The int16 source samples a workgroup of the resampling kernel keeps for a tile of `tile`
-    // outputs: the widest source span over the binding's streams, all channels (as gsc_decode_crops_fmt
-    // takes it over a call's crops).
+    // The LDS of a workgroup of the resampling kernel for a tile of `tile` outputs: the widest
+    // source_reach over the binding's streams (as gsc_decode_crops_fmt takes it over a call's crops).
     int src_samples(int64_t tile) const {
         int64_t n = 1;
-        for (const gsc::BoundShape& s : shapes) {
-            // rounded up, so that the kernel's outputs per pass come out as the whole tile
-            const int64_t reach = ((tile - 1) * s.rate_down + s.rate_up - 1) / s.rate_up + 2 * s.half_taps + 2;
-            n = std::max(n, std::min<int64_t>(reach * s.channels, gsc::kResampleSrcCap));
-        }
+        for (const gsc::BoundShape& s : shapes)
+            n = std::max(n, gsc::source_reach(tile, s.rate_up, s.rate_down, s.half_taps, s.channels));
         return int(n);
     }
 };
@@ -489,24 +517,17 @@ void gsc_stream_free(gsc_stream* st) {
         set_last_error("gsc_stream_free: the stream belongs to a stream set; free the set");
         return;
     }
-    int cur = 0;
-    const bool sw = hipGetDevice(&cur) == hipSuccess && cur != st->device;
-    if (sw) (void)hipSetDevice(st->device);
-    (void)hipDeviceSynchronize();  // queued crop decodes still read the slabs
-    delete st;
-    if (sw) (void)hipSetDevice(cur);
+    free_on_device(st);
 }
 
 // A stream's index to the device, at position 0 of `s`: the bytes and the
 // checkpoints, with_tables also the codebooks and attenuations; the frame table.
-static int upload_resident(const uint8_t* gsc, const Index& ix, bool with_tables, Slabs<ResFrame>* s,
-                           int* lds_bytes) {
+static int upload_resident(const uint8_t* gsc, const Index& ix, bool with_tables, Slabs<ResFrame>* s) {
     std::vector<ResFrame> frames(ix.frames.size());
     for (size_t i = 0; i < frames.size(); ++i) {
         const IndexFrame& f = ix.frames[i];
         static_cast<FrameTables&>(frames[i]) = frame_tables(f, SlabPos{});
         frames[i].first_sample = f.first_sample;
-        if (lds_bytes) *lds_bytes = std::max(*lds_bytes, frame_lds_bytes(f));
     }
     Span all = span_of(ix, 0, int(frames.size()));  // the whole stream
     if (!with_tables) all.count.cb = all.count.att = 0;
@@ -550,11 +571,10 @@ static int open_index(const uint8_t* gsc, size_t len, const uint8_t* table, size
 }
 
 // upload, and with a table the check on the device; the timing of both
-static int open_device(const uint8_t* gsc, const Index& ix, bool with_table, bool with_tables, Slabs<ResFrame>* s,
-                       int* lds_bytes) {
+static int open_device(const uint8_t* gsc, const Index& ix, bool with_table, bool with_tables, Slabs<ResFrame>* s) {
     if (require_device() != 0) return -1;
     const double t1 = now_ms();
-    if (upload_resident(gsc, ix, with_tables, s, lds_bytes) != 0) return -1;
+    if (upload_resident(gsc, ix, with_tables, s) != 0) return -1;
     const double t2 = now_ms();
     t_otim.upload_ms = t2 - t1;
     t_otim.uploaded_bytes = s->h2d_bytes;
@@ -572,7 +592,7 @@ static int stream_open(const uint8_t* gsc, size_t len, const uint8_t* table, siz
     t_dtim.host_index_ms = t_otim.host_ms;
     if (require_device() != 0) return -1;
     DEC_TRY(hipGetDevice(&h->device));
-    if (open_device(gsc, ix, table != nullptr, true, &h->slabs, &h->lds_bytes) != 0) return -1;
+    if (open_device(gsc, ix, table != nullptr, true, &h->slabs) != 0) return -1;
     h->view(h->slabs, 0);
     t_dtim.h2d_ms = t_otim.upload_ms;
     t_dtim.h2d_bytes = h->slabs.h2d_bytes;
@@ -738,7 +758,6 @@ gsc_stream_set* gsc_stream_set_open(const uint8_t* const* gscs, const size_t* le
     for (int i = 0; i < count; ++i) {
         gsc_stream& m = set->members[i];
         m.device = set->device;
-        for (const IndexFrame& f : m.idx.ix.frames) m.lds_bytes = std::max(m.lds_bytes, frame_lds_bytes(f));
         m.view(set->slabs, lay.frame0[size_t(i)]);
         m.set = set.get();
     }
@@ -757,13 +776,7 @@ gsc_stream* gsc_stream_set_stream(gsc_stream_set* set, int i) {
 }
 
 void gsc_stream_set_free(gsc_stream_set* set) {
-    if (!set) return;
-    int cur = 0;
-    const bool sw = hipGetDevice(&cur) == hipSuccess && cur != set->device;
-    if (sw) (void)hipSetDevice(set->device);
-    (void)hipDeviceSynchronize();  // queued crop decodes still read the slabs
-    delete set;
-    if (sw) (void)hipSetDevice(cur);
+    if (set) free_on_device(set);
 }
 
 void gsc_last_set_open_timing(gsc_set_open_timing* t) {
@@ -794,7 +807,7 @@ gsc_index* gsc_index_create_with_table(const uint8_t* gsc, size_t len, const uin
     const double t0 = now_ms();
     std::unique_ptr<gsc_index> h(new gsc_index());
     Slabs<ResFrame> s;  // the bytes and the checkpoints, for the check alone
-    if (open_index(gsc, len, table, table_len, &h->ix) != 0 || open_device(gsc, h->ix, true, false, &s, nullptr) != 0)
+    if (open_index(gsc, len, table, table_len, &h->ix) != 0 || open_device(gsc, h->ix, true, false, &s) != 0)
         return nullptr;
     t_otim.total_ms = now_ms() - t0;
     return h.release();
@@ -835,39 +848,38 @@ const gsc_index* gsc_stream_index(const gsc_stream* st) {
 
 int gsc_stream_device(const gsc_stream* st) { return st ? st->device : set_last_error("null stream"); }
 
-int gsc_decode_crops_variant(int variant) {
-    const int prev = t_crop_variant;
-    if (variant >= 0 && variant <= 2) t_crop_variant = variant;
-    return prev;
-}
-
-int gsc_decode_crops(gsc_stream* const* streams, int nstreams, const gsc_crop* crops, int ncrops, int dtype,
-                     int layout, long long length, void* dst_device, void* hip_stream, long long* written) {
+// gsc_decode_crops (has_fmt false: fmt holds its dtype, layout and length, no rate, no channels)
+// and gsc_decode_crops_fmt under the name `name`: validate, plan, check the device, describe every
+// crop in a CropJob, upload the jobs and launch.  One body fills one descriptor: the native
+// call's jobs carry the resampler's fields too (the source range, 1 / 1 / 0, no table, both
+// channel counts), which crop_fused_kernel never reads.
+static int decode_crops(const char* name, gsc_stream* const* streams, int nstreams, const gsc_crop* crops,
+                        int ncrops, const gsc_crop_format& fmt, bool has_fmt, void* dst_device, void* hip_stream,
+                        long long* written) {
     const double t_begin = now_ms();
-    t_dtim = gsc_decode_timing{};
-    if (!streams || nstreams <= 0) return set_last_error("gsc_decode_crops: no streams");
-    if (dtype != GSC_PCM_INT16 && dtype != GSC_PCM_FLOAT32) return set_last_error("gsc_decode_crops: unknown dtype");
-    if (layout != GSC_LAYOUT_TC && layout != GSC_LAYOUT_CT) return set_last_error("gsc_decode_crops: unknown layout");
-    if (!dst_device) return set_last_error("gsc_decode_crops: dst_device is null");
+    const std::string who = name;
+    if (!streams || nstreams <= 0) return set_last_error(who + ": no streams");
+    if (check_pcm_format(name, fmt.dtype, fmt.layout) != 0) return -1;
+    if (!dst_device) return set_last_error(who + ": dst_device is null");
     std::vector<const Index*> ixs(static_cast<size_t>(nstreams), nullptr);
     for (int s = 0; s < nstreams; ++s) {
-        if (!streams[s]) return set_last_error("gsc_decode_crops: stream " + std::to_string(s) + " is null");
+        if (!streams[s]) return set_last_error(who + ": stream " + std::to_string(s) + " is null");
         ixs[size_t(s)] = &streams[s]->idx.ix;
     }
     std::vector<Crop> cr(static_cast<size_t>(std::max(ncrops, 0)));
-    if (ncrops > 0 && !crops) return set_last_error("gsc_decode_crops: crops is null");
+    if (ncrops > 0 && !crops) return set_last_error(who + ": crops is null");
     for (int i = 0; i < ncrops; ++i) cr[size_t(i)] = Crop{crops[i].stream, crops[i].begin, crops[i].count};
+    const int64_t length = fmt.length;
     CropPlan plan;
     std::string err;
-    if (plan_crops(ixs.data(), nstreams, cr.data(), ncrops, length, &plan, &err) != 0) return set_last_error(err);
+    if (plan_crops(ixs.data(), nstreams, cr.data(), ncrops, length, fmt.out_rate, fmt.out_channels, &plan, &err) != 0)
+        return set_last_error(err);
     if (require_device() != 0) return -1;
     int dev = 0;
     DEC_TRY(hipGetDevice(&dev));
     for (int s = 0; s < nstreams; ++s)
         if (streams[s]->device != dev)
-            return set_last_error("gsc_decode_crops: stream " + std::to_string(s) + " lives on device " +
-                                  std::to_string(streams[s]->device) + ", the calling thread is bound to device " +
-                                  std::to_string(dev));
+            return set_last_error(other_device(who + ": stream " + std::to_string(s), streams[s]->device, dev));
     auto report = [&] {  // only once everything is enqueued: a failed call reports no output
         for (int i = 0; i < ncrops; ++i)
             if (written) written[i] = plan.crops[size_t(i)].count;
@@ -875,29 +887,37 @@ int gsc_decode_crops(gsc_stream* const* streams, int nstreams, const gsc_crop* c
     };
     if (ncrops == 0 || length == 0) return report();
     const int C = plan.channels;
-    if (C <= 0 || length > (int64_t(1) << 40) / (int64_t(ncrops) * C))
-        return set_last_error("gsc_decode_crops: output too large for one call");
+    if (C <= 0 || (has_fmt && C > 255) || length > (int64_t(1) << 40) / (int64_t(ncrops) * C))
+        return set_last_error(who + ": output too large for one call");
+    // the tables of the rates this call resamples from: the one place that may upload and block (first use)
+    std::vector<const int32_t*> tables(static_cast<size_t>(nstreams), nullptr);
+    for (const PlanCrop& pc : plan.crops)
+        if (pc.half_taps > 0 && !tables[size_t(pc.stream)] &&
+            device_resample_table(ixs[size_t(pc.stream)]->rate, fmt.out_rate, &tables[size_t(pc.stream)]) != 0)
+            return -1;
     hipStream_t hs = static_cast<hipStream_t>(hip_stream);
-    // the call's own block: job descriptors, then the symbol scratch; stream-ordered, so calls on other
-    // streams never share it
-    const size_t njob = size_t(ncrops), npc = plan.pieces.size();
-    const size_t desc_bytes = (njob * sizeof(CropJob) + npc * sizeof(CropPiece) + 15) & ~size_t(15);
-    const bool fused = t_crop_variant == 2;  // no symbol scratch
-    const size_t sym_bytes = fused ? 0 : size_t(plan.slots) * kDecodeS * sizeof(uint16_t);
+    // the call's own block, the job descriptors: stream-ordered, so calls on other streams never share it
+    const size_t njob = size_t(ncrops);
+    const size_t desc_bytes = (njob * sizeof(CropJob) + 15) & ~size_t(15);
     std::vector<unsigned char> host(desc_bytes, 0);
     CropJob* hj = reinterpret_cast<CropJob*>(host.data());
-    int lds_bytes = 0;
+    const int64_t tile = std::min<int64_t>(length, kResampleTile);
+    int64_t src_samples = 1;  // the resampling kernel's LDS: the widest source span of a full tile, all channels
+    int frames = 0;
     for (size_t i = 0; i < njob; ++i) {
         const PlanCrop& pc = plan.crops[i];
         const gsc_stream& st = *streams[pc.stream];
+        const int sch = st.idx.ix.channels;
         hj[i] = CropJob{st.frames, st.cps,   st.words, st.cb,    st.att, st.ncp, st.nwords, st.ncb,
                         st.natt,   pc.begin, pc.count, int32_t(st.idx.ix.frames.size()),
-                        pc.f0,     pc.f1,    pc.piece0};
-        lds_bytes = std::max(lds_bytes, st.lds_bytes);
+                        pc.f0,     pc.f1,    pc.src_begin, pc.src_end, tables[size_t(pc.stream)],
+                        pc.rate_up, pc.rate_down, pc.half_taps, sch, C};
+        if (has_fmt)
+            src_samples = std::max(src_samples, source_reach(tile, pc.rate_up, pc.rate_down, pc.half_taps, sch));
+        frames += pc.f1 - pc.f0;
     }
-    if (npc) std::memcpy(host.data() + njob * sizeof(CropJob), plan.pieces.data(), npc * sizeof(CropPiece));
     unsigned char* d_block = nullptr;
-    DEC_TRY(hipMallocAsync(reinterpret_cast<void**>(&d_block), desc_bytes + std::max<size_t>(sym_bytes, 16), hs));
+    DEC_TRY(hipMallocAsync(reinterpret_cast<void**>(&d_block), desc_bytes, hs));
     struct FreeAsync {
         unsigned char* p;
         hipStream_t s;
@@ -907,26 +927,27 @@ int gsc_decode_crops(gsc_stream* const* streams, int nstreams, const gsc_crop* c
     // one it cannot stage it completes first, and then this call waits for the stream's earlier work)
     DEC_TRY(hipMemcpyAsync(d_block, host.data(), desc_bytes, hipMemcpyHostToDevice, hs));
     const CropJob* d_jobs = reinterpret_cast<const CropJob*>(d_block);
-    const CropPiece* d_pieces = reinterpret_cast<const CropPiece*>(d_block + njob * sizeof(CropJob));
-    uint16_t* d_sym = reinterpret_cast<uint16_t*>(d_block + desc_bytes);
-    const int is_float = dtype == GSC_PCM_FLOAT32, planar = layout == GSC_LAYOUT_CT;
-    if (fused) {
-        // a workgroup per 4 Ki samples of a crop: 8 or 9 segments of a stereo ChunkSize-8 stream
-        DEC_TRY(gsc_launch_crop_fused(d_jobs, ncrops, length, C, is_float, planar, int(std::min<int64_t>(length, 4096)),
-                                      dst_device, hs));
+    const int is_float = fmt.dtype == GSC_PCM_FLOAT32, planar = fmt.layout == GSC_LAYOUT_CT;
+    if (has_fmt) {
+        DEC_TRY(gsc_launch_crop_resample(d_jobs, ncrops, length, C, is_float, planar, int(src_samples), dst_device,
+                                         hs));
     } else {
-        DEC_TRY(gsc_launch_crop_unpack(d_jobs, ncrops, d_pieces, int(npc), d_sym, plan.slots, hs));
-        // LDS variant: a workgroup per 16 Ki samples of a crop
-        DEC_TRY(gsc_launch_crop_synth(d_jobs, ncrops, d_pieces, int(npc), d_sym, plan.slots, length, C, is_float,
-                                      planar, t_crop_variant == 1 ? lds_bytes : -1,
-                                      int(std::min<int64_t>(length, 16384)), dst_device, hs));
+        DEC_TRY(gsc_launch_crop_fused(d_jobs, ncrops, length, C, is_float, planar,
+                                      int(std::min<int64_t>(length, kCropTile)), dst_device, hs));
     }
     t_dtim.h2d_bytes = (long long)desc_bytes;
-    t_dtim.frames = int(npc);
-    t_dtim.symbols = plan.slots * kDecodeS;
+    t_dtim.frames = frames;
     t_dtim.samples = int64_t(ncrops) * length * C;
     t_dtim.total_ms = now_ms() - t_begin;
     return report();
+}
+
+int gsc_decode_crops(gsc_stream* const* streams, int nstreams, const gsc_crop* crops, int ncrops, int dtype,
+                     int layout, long long length, void* dst_device, void* hip_stream, long long* written) {
+    t_dtim = gsc_decode_timing{};
+    const gsc_crop_format fmt{dtype, layout, length, 0, 0};
+    return decode_crops("gsc_decode_crops", streams, nstreams, crops, ncrops, fmt, false, dst_device, hip_stream,
+                        written);
 }
 
 int gsc_resample_tile(void) { return kResampleTile; }
@@ -949,87 +970,10 @@ int gsc_resample_prepare(int in_rate, int out_rate) {
 
 int gsc_decode_crops_fmt(gsc_stream* const* streams, int nstreams, const gsc_crop* crops, int ncrops,
                          const gsc_crop_format* fmt, void* dst_device, void* hip_stream, long long* written) {
-    const double t_begin = now_ms();
     t_dtim = gsc_decode_timing{};
     if (!fmt) return set_last_error("gsc_decode_crops_fmt: format is null");
-    if (!streams || nstreams <= 0) return set_last_error("gsc_decode_crops_fmt: no streams");
-    if (fmt->dtype != GSC_PCM_INT16 && fmt->dtype != GSC_PCM_FLOAT32)
-        return set_last_error("gsc_decode_crops_fmt: unknown dtype");
-    if (fmt->layout != GSC_LAYOUT_TC && fmt->layout != GSC_LAYOUT_CT)
-        return set_last_error("gsc_decode_crops_fmt: unknown layout");
-    if (!dst_device) return set_last_error("gsc_decode_crops_fmt: dst_device is null");
-    std::vector<const Index*> ixs(static_cast<size_t>(nstreams), nullptr);
-    for (int s = 0; s < nstreams; ++s) {
-        if (!streams[s]) return set_last_error("gsc_decode_crops_fmt: stream " + std::to_string(s) + " is null");
-        ixs[size_t(s)] = &streams[s]->idx.ix;
-    }
-    std::vector<Crop> cr(static_cast<size_t>(std::max(ncrops, 0)));
-    if (ncrops > 0 && !crops) return set_last_error("gsc_decode_crops_fmt: crops is null");
-    for (int i = 0; i < ncrops; ++i) cr[size_t(i)] = Crop{crops[i].stream, crops[i].begin, crops[i].count};
-    const int64_t length = fmt->length;
-    CropPlan plan;
-    std::string err;
-    if (plan_crops_fmt(ixs.data(), nstreams, cr.data(), ncrops, length, fmt->out_rate, fmt->out_channels, &plan,
-                       &err) != 0)
-        return set_last_error(err);
-    if (require_device() != 0) return -1;
-    int dev = 0;
-    DEC_TRY(hipGetDevice(&dev));
-    for (int s = 0; s < nstreams; ++s)
-        if (streams[s]->device != dev)
-            return set_last_error("gsc_decode_crops_fmt: stream " + std::to_string(s) + " lives on device " +
-                                  std::to_string(streams[s]->device) + ", the calling thread is bound to device " +
-                                  std::to_string(dev));
-    auto report = [&] {  // only once everything is enqueued: a failed call reports no output
-        for (int i = 0; i < ncrops; ++i)
-            if (written) written[i] = plan.crops[size_t(i)].count;
-        return 0;
-    };
-    if (ncrops == 0 || length == 0) return report();
-    const int C = plan.channels;
-    if (C <= 0 || C > 255 || length > (int64_t(1) << 40) / (int64_t(ncrops) * C))
-        return set_last_error("gsc_decode_crops_fmt: output too large for one call");
-    // the tables of the rates this call resamples from: the one place that may upload and block (first use)
-    std::vector<const int32_t*> tables(static_cast<size_t>(nstreams), nullptr);
-    for (const PlanCrop& pc : plan.crops)
-        if (pc.half_taps > 0 && !tables[size_t(pc.stream)] &&
-            device_resample_table(ixs[size_t(pc.stream)]->rate, fmt->out_rate, &tables[size_t(pc.stream)]) != 0)
-            return -1;
-    hipStream_t hs = static_cast<hipStream_t>(hip_stream);
-    const size_t njob = size_t(ncrops);
-    const size_t desc_bytes = (njob * sizeof(CropJob) + 15) & ~size_t(15);
-    std::vector<unsigned char> host(desc_bytes, 0);
-    CropJob* hj = reinterpret_cast<CropJob*>(host.data());
-    int64_t src_samples = 1;  // the LDS of a workgroup: the widest source span of a full tile, all channels
-    for (size_t i = 0; i < njob; ++i) {
-        const PlanCrop& pc = plan.crops[i];
-        const gsc_stream& st = *streams[pc.stream];
-        const int sch = st.idx.ix.channels;
-        hj[i] = CropJob{st.frames, st.cps,   st.words, st.cb,    st.att, st.ncp, st.nwords, st.ncb,
-                        st.natt,   pc.begin, pc.count, int32_t(st.idx.ix.frames.size()),
-                        pc.f0,     pc.f1,    0,        pc.src_begin, pc.src_end, tables[size_t(pc.stream)],
-                        pc.rate_up, pc.rate_down, pc.half_taps, sch, C};
-        const int64_t tile = std::min<int64_t>(length, kResampleTile);
-        // rounded up, so that the kernel's outputs per pass come out as the whole tile
-        const int64_t reach = ((tile - 1) * pc.rate_down + pc.rate_up - 1) / pc.rate_up + 2 * pc.half_taps + 2;
-        src_samples = std::max(src_samples, std::min<int64_t>(reach * sch, kResampleSrcCap));
-    }
-    unsigned char* d_block = nullptr;
-    DEC_TRY(hipMallocAsync(reinterpret_cast<void**>(&d_block), desc_bytes, hs));
-    struct FreeAsync {
-        unsigned char* p;
-        hipStream_t s;
-        ~FreeAsync() { (void)hipFreeAsync(p, s); }
-    } guard{d_block, hs};
-    // pageable source, as in gsc_decode_crops
-    DEC_TRY(hipMemcpyAsync(d_block, host.data(), desc_bytes, hipMemcpyHostToDevice, hs));
-    DEC_TRY(gsc_launch_crop_resample(reinterpret_cast<const CropJob*>(d_block), ncrops, length, C,
-                                     fmt->dtype == GSC_PCM_FLOAT32, fmt->layout == GSC_LAYOUT_CT, int(src_samples),
-                                     dst_device, hs));
-    t_dtim.h2d_bytes = (long long)desc_bytes;
-    t_dtim.samples = int64_t(ncrops) * length * C;
-    t_dtim.total_ms = now_ms() - t_begin;
-    return report();
+    return decode_crops("gsc_decode_crops_fmt", streams, nstreams, crops, ncrops, *fmt, true, dst_device, hip_stream,
+                        written);
 }
 
 int gsc_crop_plan_model(const gsc_index* ix, int nstreams, int stream, long long begin, long long count,
@@ -1037,7 +981,7 @@ int gsc_crop_plan_model(const gsc_index* ix, int nstreams, int stream, long long
                         long long* src_end) {
     if (!ix || out_rate < 0 || length < 0) return set_last_error("gsc_crop_plan_model: invalid argument");
     const Index& x = ix->ix;
-    ResampleShape sh;  // a stream without samples has no rate of its own, as in plan_crops_fmt
+    ResampleShape sh;  // a stream without samples has no rate of its own, as in plan_crops
     std::string err;
     if (out_rate != 0 && x.rate != out_rate && x.samples > 0 && resample_shape(x.rate, out_rate, &sh, &err) != 0)
         return set_last_error(err);
@@ -1082,7 +1026,7 @@ gsc_crop_binding* gsc_crop_binding_create(gsc_stream* const* streams, int nstrea
         const gsc_stream& st = *streams[s];
         const Index& ix = st.idx.ix;
         const int cs = ix.channels;
-        // plan_crops' and plan_crops_fmt's refusals per stream, and gsc_decode_crops' of another device
+        // plan_crops' refusals per stream, and gsc_decode_crops' of another device
         if (out_channels == 0 && cs != b->channels)
             return fail(named(s) + " has " + std::to_string(cs) + " channels, stream 0 has " +
                         std::to_string(b->channels));
@@ -1101,8 +1045,7 @@ gsc_crop_binding* gsc_crop_binding_create(gsc_stream* const* streams, int nstrea
         if (ix.samples > (int64_t(1) << 40) || ix.frames.size() >= (size_t(1) << 31))
             return fail(named(s) + ": too long for one call");
         if (st.device != dev)
-            return fail(named(s) + " lives on device " + std::to_string(st.device) +
-                        ", the calling thread is bound to device " + std::to_string(dev));
+            return fail(other_device(named(s), st.device, dev));
         // every table a call will read is on the device before the first call
         if (sh.half_taps > 0 && device_resample_table(ix.rate, out_rate, &table) != 0) {
             set_last_error(named(s) + ": " + gsc_last_error());
@@ -1134,10 +1077,7 @@ int gsc_crop_binding_decode(gsc_crop_binding* b, const long long* crops_device, 
     const double t_begin = now_ms();
     gsc_crop_call_stats& stats = t_bstat = gsc_crop_call_stats{};
     if (!b) return set_last_error("gsc_crop_binding_decode: binding is null");
-    if (dtype != GSC_PCM_INT16 && dtype != GSC_PCM_FLOAT32)
-        return set_last_error("gsc_crop_binding_decode: unknown dtype");
-    if (layout != GSC_LAYOUT_TC && layout != GSC_LAYOUT_CT)
-        return set_last_error("gsc_crop_binding_decode: unknown layout");
+    if (check_pcm_format("gsc_crop_binding_decode", dtype, layout) != 0) return -1;
     if (ncrops < 0 || length < 0) return set_last_error("gsc_crop_binding_decode: invalid argument");
     if (ncrops > 0 && length > 0) {
         if (!crops_device) return set_last_error("gsc_crop_binding_decode: crops_device is null");
@@ -1148,8 +1088,7 @@ int gsc_crop_binding_decode(gsc_crop_binding* b, const long long* crops_device, 
         int dev = 0;
         DEC_TRY(hipGetDevice(&dev));
         if (dev != b->device)
-            return set_last_error("gsc_crop_binding_decode: the binding lives on device " + std::to_string(b->device) +
-                                  ", the calling thread is bound to device " + std::to_string(dev));
+            return set_last_error(other_device("gsc_crop_binding_decode: the binding", b->device, dev));
         hipStream_t hs = static_cast<hipStream_t>(hip_stream);
         const int is_float = dtype == GSC_PCM_FLOAT32, planar = layout == GSC_LAYOUT_CT;
         const int64_t* crops = reinterpret_cast<const int64_t*>(crops_device);
@@ -1160,9 +1099,8 @@ int gsc_crop_binding_decode(gsc_crop_binding* b, const long long* crops_device, 
                                                    b->src_samples(std::min<int64_t>(length, kResampleTile)),
                                                    dst_device, written, hs));
         } else {
-            // a workgroup per 4 Ki samples of a crop, as gsc_decode_crops
             DEC_TRY(gsc_launch_crop_fused_bound(b->streams.p, b->nstreams, crops, ncrops, length, C, is_float, planar,
-                                                int(std::min<int64_t>(length, 4096)), dst_device, written, hs));
+                                                int(std::min<int64_t>(length, kCropTile)), dst_device, written, hs));
         }
         ++stats.launches;
     }
@@ -1203,8 +1141,7 @@ int gsc_crop_binding_envelope(gsc_crop_binding* b, int hop, long long* energy_de
     int dev = 0;
     DEC_TRY(hipGetDevice(&dev));
     if (dev != b->device)
-        return set_last_error("gsc_crop_binding_envelope: the binding lives on device " + std::to_string(b->device) +
-                              ", the calling thread is bound to device " + std::to_string(dev));
+        return set_last_error(other_device("gsc_crop_binding_envelope: the binding", b->device, dev));
     // once per corpus: the call may ask the runtime where its outputs live
     const std::pair<const void*, const char*> outs[2] = {{energy_device, "energy_device"}, {peak_device, "peak_device"}};
     for (const auto& o : outs) {
@@ -1230,13 +1167,7 @@ int gsc_crop_binding_envelope(gsc_crop_binding* b, int hop, long long* energy_de
 }
 
 void gsc_crop_binding_free(gsc_crop_binding* b) {
-    if (!b) return;
-    int cur = 0;
-    const bool sw = hipGetDevice(&cur) == hipSuccess && cur != b->device;
-    if (sw) (void)hipSetDevice(b->device);
-    (void)hipDeviceSynchronize();  // queued calls still read the descriptors
-    delete b;
-    if (sw) (void)hipSetDevice(cur);
+    if (b) free_on_device(b);
 }
 
 int gsc_stream_decode_samples(gsc_stream* st, long long begin, long long count, int16_t* pcm) {

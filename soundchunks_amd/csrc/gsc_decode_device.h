@@ -175,7 +175,8 @@ __device__ __forceinline__ int16_t table_sample(const FrameTables& f, const int*
 
 // Segment seg of frame f of a crop's stream to o[0 .. kDecodeS); false (nothing
 // written) when the segment or its checkpoint lies outside the stream's slabs.
-__device__ __forceinline__ bool crop_unpack_one(const CropJob& job, const ResFrame& f, int64_t seg, uint16_t* o) {
+__device__ __forceinline__ bool unpack_crop_segment(const CropJob& job, const ResFrame& f, int64_t seg,
+                                                    uint16_t* o) {
     if (seg < 0 || seg > f.nsym / kDecodeS) return false;
     const int64_t s0 = seg * kDecodeS;
     if (s0 >= f.nsym) return false;
@@ -237,12 +238,12 @@ __device__ __forceinline__ void crop_write_run(int64_t ta, int64_t tb, int chann
 
 // ---- the fused walk of a frame (crop_fused_kernel, crop_fused_bound_kernel, envelope_kernel) ----
 
-// The fused variant: no symbol scratch and no unpack launch.  A workgroup
-// takes a run of tile_len samples of one crop; per frame the run crosses, and
-// per stretch of symbol rows whose symbols span at most kFusedSegs checkpoint
-// segments, its first lanes unpack those segments into LDS (one lane per
-// segment, as crop_unpack_kernel), then all lanes write the stretch's samples
-// with the codebook read from global memory.
+// No symbol scratch and no unpack launch.  A workgroup takes a run of tile_len
+// samples of one crop; per frame the run crosses, and per stretch of symbol
+// rows whose symbols span at most kFusedSegs checkpoint segments, its first
+// lanes unpack those segments into LDS (one lane per segment, as
+// decode_unpack_kernel), then all lanes write the stretch's samples with the
+// codebook read from global memory.
 constexpr int kFusedThreads = 256;
 constexpr int kFusedSegs = 64;
 
@@ -264,7 +265,7 @@ __device__ __forceinline__ auto fused_frame(uint16_t* ssym, int* slut, int tid) 
             if (tid < 32) slut[tid] = f.lut[tid];
             for (int i = tid; i < (int)nseg; i += kFusedThreads) {
                 uint16_t* o = ssym + i * kDecodeS;
-                if (!crop_unpack_one(job, f, seg_lo + i, o))
+                if (!unpack_crop_segment(job, f, seg_lo + i, o))
                     for (int z = 0; z < kDecodeS; ++z) o[z] = 0;
             }
             __syncthreads();
@@ -297,7 +298,7 @@ __device__ __forceinline__ const P* wave_uniform(const P* p) {
 }
 
 // One lane: the CropJob of crop c = (stream, begin, count) of a bound call, as
-// plan_crops / plan_crops_fmt and the host fill it for the other calls.
+// plan_crops and the host fill it for the other calls.
 // Returns what the call reports as written: the clipped count, or -1 for a bad
 // crop, whose job is empty (f0 == f1), so that the kernels zero its row and
 // read nothing through it.  The stream index is checked before it is used, the
@@ -315,7 +316,7 @@ __device__ __forceinline__ int64_t bound_plan(const BoundStream* __restrict__ st
         if (crop_plan_one(begin, count, length, d.samples, d.nframes, d.rate_up, d.rate_down, d.half_taps,
                           [&](int i) { return frames[i].first_sample; }, &sp) == kCropGood) {
             j = CropJob{frames,     d.cps,     d.words,  d.cb,      d.att, d.ncp, d.nwords,     d.ncb,
-                        d.natt,     begin,     sp.count, d.nframes, sp.f0, sp.f1, 0,            sp.src_begin,
+                        d.natt,     begin,     sp.count, d.nframes, sp.f0, sp.f1, sp.src_begin,
                         sp.src_end, d.table,   d.rate_up, d.rate_down, d.half_taps, d.channels, out_ch};
             written = sp.count;
         }
@@ -348,7 +349,6 @@ __device__ __forceinline__ CropJob shared_job_load(const CropJob* sjob) {
     j.nframes = wave_uniform(sjob->nframes);
     j.f0 = wave_uniform(sjob->f0);
     j.f1 = wave_uniform(sjob->f1);
-    j.piece0 = 0;
     j.src_begin = wave_uniform(sjob->src_begin);
     j.src_end = wave_uniform(sjob->src_end);
     j.table = wave_uniform(sjob->table);

@@ -141,7 +141,7 @@ __global__ __launch_bounds__(kFusedThreads) void envelope_kernel(const BoundStre
                 sp.count > 0) {
                 j = CropJob{frames,     d.cps,   d.words,  d.cb,      d.att, d.ncp, d.nwords, d.ncb,
                             d.natt,     tile * tile_len,   sp.count,  d.nframes,    sp.f0,    sp.f1,
-                            0,          sp.src_begin,      sp.src_end, nullptr,     1,        1,
+                            sp.src_begin,      sp.src_end, nullptr,     1,        1,
                             0,          d.channels,        d.channels};
             }
         }

@@ -1,5 +1,5 @@
 // .gsc decoder, the host index (decoder/decoder.lpr:37-220):
-// the sequential walk, the sample locator and the crop planner.  Plain C++,
+// the sequential walk, seek tables and the sample locator.  Plain C++,
 // no device needed; gsc_decode_abi.cpp holds the HIP runtime side.
 //
 // A .gsc is a concatenation of frames: 12-byte header, attenuation nibbles,
@@ -13,8 +13,8 @@
 // segment, one lane writes one output sample (gsc_decode.hip).
 //
 // For sample ranges of a resident stream, index_locate finds the checkpoint
-// at or before a sample and plan_crops lays out what a batch of ranges has to
-// unpack (gsc_decode_crops.hip).
+// at or before a sample; a batch of ranges is planned by plan_crops
+// (gsc_resample.cpp) for gsc_decode_crops.hip.
 #include "gsc_decode.h"
 
 #include <algorithm>
@@ -448,70 +448,6 @@ int index_locate(const Index& ix, int64_t sample, int* frame, int64_t* row, int*
     if (row) *row = r;
     if (within) *within = int(local - r * f.cs);
     if (checkpoint) *checkpoint = int64_t(f.cp_first) + r * f.ch / kDecodeS;
-    return 0;
-}
-
-int plan_crops(const Index* const* ixs, int nstreams, const Crop* crops, int ncrops, int64_t length, CropPlan* plan,
-               std::string* err) {
-    *plan = CropPlan();
-    auto refuse = [&](int i, const std::string& what) {
-        if (err) *err = "gsc crops: crop " + std::to_string(i) + ": " + what;
-        return -1;
-    };
-    if (!ixs || nstreams <= 0 || ncrops < 0 || (ncrops > 0 && !crops) || length < 0) {
-        if (err) *err = "gsc crops: invalid argument";
-        return -1;
-    }
-    for (int s = 0; s < nstreams; ++s) {
-        if (!ixs[s]) {
-            if (err) *err = "gsc crops: stream " + std::to_string(s) + " is null";
-            return -1;
-        }
-        if (ixs[s]->channels != ixs[0]->channels) {
-            if (err)
-                *err = "gsc crops: stream " + std::to_string(s) + " has " + std::to_string(ixs[s]->channels) +
-                       " channels, stream 0 has " + std::to_string(ixs[0]->channels);
-            return -1;
-        }
-    }
-    plan->channels = ixs[0]->channels;
-    plan->crops.reserve(size_t(ncrops));
-    for (int i = 0; i < ncrops; ++i) {
-        const Crop& c = crops[i];
-        if (c.stream < 0 || c.stream >= nstreams) return refuse(i, "stream index " + std::to_string(c.stream));
-        const Index& ix = *ixs[c.stream];
-        if (c.begin < 0 || c.begin > ix.samples)
-            return refuse(i, "begin " + std::to_string(c.begin) + " outside [0, " + std::to_string(ix.samples) + "]");
-        if (c.count < 0 || c.count > length)
-            return refuse(i, "count " + std::to_string(c.count) + " outside [0, length " + std::to_string(length) + "]");
-        PlanCrop pc{c.stream, c.begin, std::min<int64_t>(c.count, ix.samples - c.begin), 0, 0, int(plan->pieces.size())};
-        if (pc.count > 0) {
-            int fa = 0, fb = 0;
-            int64_t ra = 0, rb = 0;
-            if (index_locate(ix, pc.begin, &fa, &ra, nullptr, nullptr, err) != 0 ||
-                index_locate(ix, pc.begin + pc.count - 1, &fb, &rb, nullptr, nullptr, err) != 0)
-                return -1;
-            pc.f0 = fa;
-            pc.f1 = fb + 1;
-            for (int fi = fa; fi <= fb; ++fi) {
-                const IndexFrame& f = ix.frames[size_t(fi)];
-                CropPiece p{plan->slots, 0, 0, i, fi, 0};
-                if (f.nsym > 0) {
-                    // symbol rows [r0, r1] of this frame, whole checkpoint segments around them
-                    const int64_t r0 = fi == fa ? ra : 0, r1 = fi == fb ? rb : int64_t(f.flen) - 1;
-                    p.seg0 = r0 * f.ch / kDecodeS;
-                    p.nseg = int32_t(((r1 + 1) * f.ch - 1) / kDecodeS - p.seg0 + 1);
-                }
-                plan->slots += p.nseg;
-                plan->pieces.push_back(p);
-            }
-        }
-        plan->crops.push_back(pc);
-    }
-    if (plan->pieces.size() >= (size_t(1) << 31) || plan->slots >= (int64_t(1) << 40)) {
-        if (err) *err = "gsc crops: too many frames or symbols for one call";
-        return -1;
-    }
     return 0;
 }
 

@@ -1,7 +1,7 @@
 // Crops of resident .gsc streams at a common sample rate and channel count on
 // MI355X (gfx950): gsc_decode_crops_fmt's one launch, beside the native-rate
 // kernels of gsc_decode_crops.hip.  include/soundchunks.h defines the
-// resampler; gsc::plan_crops_fmt planned every crop (gsc_resample.cpp).
+// resampler; gsc::plan_crops planned every crop (gsc_resample.cpp).
 //
 //   crop_resample_kernel  a workgroup owns kResampleTile output samples of one
 //                         crop, taken in passes of as many outputs as the
@@ -67,7 +67,7 @@ __device__ __forceinline__ void resample_fill(const CropJob& job, int64_t sa, in
             if (tid < 32) slut[tid] = f.lut[tid];
             for (int i = tid; i < (int)nseg; i += kResThreads) {
                 uint16_t* o = ssym + i * kDecodeS;
-                if (!crop_unpack_one(job, f, seg_lo + i, o))
+                if (!unpack_crop_segment(job, f, seg_lo + i, o))
                     for (int z = 0; z < kDecodeS; ++z) o[z] = 0;
             }
             __syncthreads();

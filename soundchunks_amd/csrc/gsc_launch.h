@@ -22,7 +22,6 @@ struct DecJob;
 struct ResFrame;
 struct TableSrc;
 struct CropJob;
-struct CropPiece;
 struct BoundStream;
 }  // namespace gsc
 
@@ -99,11 +98,6 @@ hipError_t gsc_launch_decode_synth(const gsc::DecFrame* frames, int nframes, con
                                    const uint8_t* att, int64_t natt, int16_t* out, int64_t nout, hipStream_t st);
 
 // ---- gsc_decode_crops.hip
-hipError_t gsc_launch_crop_unpack(const gsc::CropJob* jobs, int ncrops, const gsc::CropPiece* pieces, int npieces,
-                                  uint16_t* sym, int64_t nslots, hipStream_t st);
-hipError_t gsc_launch_crop_synth(const gsc::CropJob* jobs, int ncrops, const gsc::CropPiece* pieces, int npieces,
-                                 const uint16_t* sym, int64_t nslots, int64_t length, int channels, int is_float,
-                                 int planar, int lds_bytes, int tile_len, void* out, hipStream_t st);
 hipError_t gsc_launch_crop_fused(const gsc::CropJob* jobs, int ncrops, int64_t length, int channels, int is_float,
                                  int planar, int tile_len, void* out, hipStream_t st);
 hipError_t gsc_launch_crop_fused_bound(const gsc::BoundStream* streams, int nstreams, const int64_t* crops, int ncrops,

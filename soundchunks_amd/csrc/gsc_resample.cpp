@@ -1,7 +1,8 @@
 // Crops at a common sample rate and channel count, host side (no HIP): the
-// resampler's tables and their process-wide cache, and the planner of
-// gsc_decode_crops_fmt.  The definition is in include/soundchunks.h; the
-// kernel that applies it is gsc_decode_resample.hip.
+// resampler's tables and their process-wide cache, and the host planner of
+// gsc_decode_crops and gsc_decode_crops_fmt (per crop: gsc_crop_plan.h).  The
+// resampler's definition is in include/soundchunks.h; the kernel that applies
+// it is gsc_decode_resample.hip.
 #include <algorithm>
 #include <cmath>
 #include <map>
@@ -9,6 +10,7 @@
 #include <mutex>
 #include <numeric>
 
+#include "gsc_crop_plan.h"
 #include "gsc_decode.h"
 
 namespace gsc {
@@ -107,8 +109,8 @@ int64_t resample_outputs(int64_t samples, int64_t begin, const ResampleShape& s)
     return ((samples - begin) * s.phases + s.step - 1) / s.step;
 }
 
-int plan_crops_fmt(const Index* const* ixs, int nstreams, const Crop* crops, int ncrops, int64_t length, int out_rate,
-                   int out_channels, CropPlan* plan, std::string* err) {
+int plan_crops(const Index* const* ixs, int nstreams, const Crop* crops, int ncrops, int64_t length, int out_rate,
+               int out_channels, CropPlan* plan, std::string* err) {
     *plan = CropPlan();
     auto fail = [&](const std::string& what) {
         if (err) *err = what;
@@ -150,30 +152,20 @@ int plan_crops_fmt(const Index* const* ixs, int nstreams, const Crop* crops, int
     plan->crops.reserve(size_t(ncrops));
     for (int i = 0; i < ncrops; ++i) {
         const Crop& c = crops[i];
-        if (c.stream < 0 || c.stream >= nstreams) return refuse(i, "stream index " + std::to_string(c.stream));
+        if (crop_stream_status(c.stream, nstreams) != kCropGood)
+            return refuse(i, "stream index " + std::to_string(c.stream));
         const Index& ix = *ixs[c.stream];
         const ResampleShape& sh = shapes[size_t(c.stream)];
-        if (c.begin < 0 || c.begin > ix.samples)
+        CropSpan sp;
+        const int status =
+            crop_plan_one(c.begin, c.count, length, ix.samples, int32_t(ix.frames.size()), sh.phases, sh.step,
+                          sh.half_taps, [&](int32_t f) { return ix.frames[size_t(f)].first_sample; }, &sp);
+        if (status == kCropBadBegin)
             return refuse(i, "begin " + std::to_string(c.begin) + " outside [0, " + std::to_string(ix.samples) + "]");
-        if (c.count < 0 || c.count > length)
+        if (status == kCropBadCount)
             return refuse(i, "count " + std::to_string(c.count) + " outside [0, length " + std::to_string(length) + "]");
-        PlanCrop pc{c.stream, c.begin, std::min<int64_t>(c.count, resample_outputs(ix.samples, c.begin, sh)), 0, 0, 0};
-        pc.rate_up = sh.phases;
-        pc.rate_down = sh.step;
-        pc.half_taps = sh.half_taps;
-        if (pc.count > 0) {
-            // outputs 0 .. count - 1 sit at source samples begin .. last; the filter reads T - 1 before and T after
-            const int64_t last = (pc.begin * sh.phases + (pc.count - 1) * sh.step) / sh.phases;
-            const int64_t before = sh.half_taps > 0 ? sh.half_taps - 1 : 0;
-            pc.src_begin = std::max<int64_t>(pc.begin - before, 0);
-            pc.src_end = std::min<int64_t>(last + sh.half_taps + 1, ix.samples);
-            int fa = 0, fb = 0;
-            if (index_locate(ix, pc.src_begin, &fa, nullptr, nullptr, nullptr, err) != 0 ||
-                index_locate(ix, pc.src_end - 1, &fb, nullptr, nullptr, nullptr, err) != 0)
-                return -1;
-            pc.f0 = fa;
-            pc.f1 = fb + 1;
-        }
+        const PlanCrop pc{c.stream,     c.begin,    sp.count,  sp.f0,   sp.f1,
+                          sp.src_begin, sp.src_end, sh.phases, sh.step, sh.half_taps};
         plan->crops.push_back(pc);
     }
     return 0;

@@ -588,18 +588,6 @@ class Decoder:
         _lib.load().gsc_last_open_timing(ctypes.byref(t))
         return {k: getattr(t, k) for k, _ in t._fields_}
 
-    CROP_VARIANTS = ("global", "lds", "fused")
-
-    @staticmethod
-    def crop_variant(name=None) -> str:
-        """Measurement knob, not a stable interface (``gsc_decode_crops_variant``):
-        how this thread's crop calls run.  "global": unpack, then synthesis with
-        the codebook read from global memory; "lds": the same with the codebook
-        staged in LDS; "fused" (the default): one launch, symbols through LDS.
-        Returns the previous setting; ``None`` only queries.  Same output."""
-        v = -1 if name is None else Decoder.CROP_VARIANTS.index(name)
-        return Decoder.CROP_VARIANTS[_lib.load().gsc_decode_crops_variant(v)]
-
     @staticmethod
     def resample_tile() -> int:
         """Output samples of one workgroup of the resampling crop kernel."""

@@ -188,34 +188,10 @@ def test_batch_of_two_streams(sc, pair, dtype, layout):
     assert y is out and torch.equal(x, out)
 
 
-def _other_variants(sc):
-    return [v for v in sc.Decoder.CROP_VARIANTS if v != sc.Decoder.crop_variant()]
-
-
-def test_variant_knob(sc):
-    default = sc.Decoder.crop_variant()
-    assert default in sc.Decoder.CROP_VARIANTS and len(_other_variants(sc)) == 2
-    for v in _other_variants(sc):
-        prev = sc.Decoder.crop_variant(v)
-        assert sc.Decoder.crop_variant() == v
-        sc.Decoder.crop_variant(prev)
-    assert sc.Decoder.crop_variant() == default
-
-
-@pytest.fixture(params=[0, 1])
-def other_variant(sc, request):
-    """Runs a test under one of the two crop variants that are not the default."""
-    v = _other_variants(sc)[request.param]
-    prev = sc.Decoder.crop_variant(v)
-    yield v
-    sc.Decoder.crop_variant(prev)
-
-
-def test_other_variants_large_codebooks(sc, pair, other_variant):
-    """A 4096 x 16, 12-bit frame (132 KiB of tables: the most the LDS variant
-    stages), a small frame, then 8191 x 16 (260 KiB: more than it can stage, so
-    that frame is read from global memory between two staged ones), through the
-    variants that are not the default; then the two-stream batch as well."""
+def test_large_codebooks(sc, pair):
+    """A 4096 x 16, 12-bit frame (132 KiB of tables), a small frame, then
+    8191 x 16 (260 KiB, codebook offsets beyond 2^17) and another small one in
+    one stream; then the two-stream batch as well."""
     import torch
 
     rng = np.random.default_rng(46)
@@ -231,35 +207,40 @@ def test_other_variants_large_codebooks(sc, pair, other_variant):
     _check(sc, list(pair), BATCH, 3600)
 
 
-def test_lds_limit_on_two_devices(sc):
-    """The LDS variant needs its dynamic-LDS limit raised above 32 KiB on
-    every device it runs on: the 4096 x 16, 12-bit frame (132 KiB of tables)
-    resident on device 0, then on device 1, in one process."""
+def test_native_and_own_format_on_two_devices(sc):
+    """The 4096 x 16, 12-bit frame (132 KiB of tables) resident on device 0,
+    then on device 1, in one process: on each the native call, and the same
+    crops with rate= the stream's own and channels= its own, which go through
+    the resampling kernel, the one whose dynamic-LDS limit is raised per device."""
     import torch
 
     if torch.cuda.device_count() < 2:
         pytest.skip("needs two devices")
     rng = np.random.default_rng(46)
     gsc = gw.random_frame(rng, 2 * 600, ch=2, count=4096, cs=16, bd=12, policy="once")
-    device, variant = torch.cuda.current_device(), sc.Decoder.crop_variant("lds")
+    device = torch.cuda.current_device()
+    crops = [(0, 0, 9600), (0, 9590, 10)]
     try:
         for d in (0, 1):
             torch.cuda.set_device(d)
             sc.set_device(d)
             r = Res(sc, gsc)
             assert r.st.device == d
-            _check(sc, [r], [(0, 0, 9600), (0, 9590, 10)], 9600)
+            _check(sc, [r], crops, 9600)
+            y, n = sc.Decoder.decode_crops([r.st], crops, length=9600, rate=r.st.sample_rate, channels=r.st.channels)
+            want, lens = _expected([r], crops, 9600, torch.int16, "TC")
+            assert y.dtype == torch.int16 and np.array_equal(y.cpu().numpy(), want) and n == lens
             r.st.close()
     finally:
         torch.cuda.set_device(device)
         sc.set_device(device)
-        sc.Decoder.crop_variant(variant)
 
 
-def test_other_variants_at_the_edges(sc, other_variant):
-    """The chunk, checkpoint and frame edges again under the other variants:
-    frames of different ChunkSize, ChunkCount and bit depth (the 12-bit one with
-    an odd ChunkSize in the middle) and empty frames inside one workgroup's run."""
+def test_edges_of_mixed_frames(sc):
+    """The chunk, checkpoint and frame edges again: frames of different
+    ChunkSize, ChunkCount and bit depth (the 12-bit one with an odd ChunkSize in
+    the middle, an `always`-checkpointed one) and empty frames inside one
+    workgroup's run."""
     import torch
 
     S = sc.Decoder.checkpoint_symbols()

@@ -181,7 +181,7 @@ def test_saturation(sc):
 
 
 def test_identity(sc, crafted):
-    """rate = the stream's own and channels = its own: the call without the keywords, under every variant."""
+    """rate = the stream's own and channels = its own: the call without the keywords."""
     import torch
 
     for r in (crafted(32000, 1), crafted(48000, 2)):
@@ -192,14 +192,9 @@ def test_identity(sc, crafted):
             x1 = sc.Decoder.decode_crops([r.st], crops, 1100, dtype=dtype, layout=layout, rate=r.rate)[0]
             x2 = sc.Decoder.decode_crops([r.st], crops, 1100, dtype=dtype, layout=layout, channels=r.ch)[0]
             assert torch.equal(x, x1) and torch.equal(x, x2)
-            for v in sc.Decoder.CROP_VARIANTS:
-                prev = sc.Decoder.crop_variant(v)
-                try:
-                    y, m = sc.Decoder.decode_crops([r.st], crops, 1100, dtype=dtype, layout=layout)
-                finally:
-                    sc.Decoder.crop_variant(prev)
-                assert torch.equal(x, y), v
-                assert m == [min(c, n - b) for _, b, c in crops]
+            y, m = sc.Decoder.decode_crops([r.st], crops, 1100, dtype=dtype, layout=layout)
+            assert torch.equal(x, y)
+            assert m == [min(c, n - b) for _, b, c in crops]
 
 
 def test_channels(sc, crafted):

@@ -308,15 +308,10 @@ def test_crops_across_owners(sc, owners):
     _check_crops(sc, streams, pcm, crops, 512, "float32", "CT")
 
 
-@pytest.mark.parametrize("variant", ["global", "lds", "fused"])
-def test_crop_variants_on_members(sc, owners, variant):
+def test_crops_on_members(sc, owners):
     streams, pcm = owners
-    prev = sc.Decoder.crop_variant(variant)
-    try:
-        _check_crops(sc, streams, pcm, [(0, 1190, 100), (2, 5, 90), (3, len(pcm[3]) - 7, 30), (1, 40, 100)], 100,
-                     "int16", "TC")
-    finally:
-        sc.Decoder.crop_variant(prev)
+    _check_crops(sc, streams, pcm, [(0, 1190, 100), (2, 5, 90), (3, len(pcm[3]) - 7, 30), (1, 40, 100)], 100,
+                 "int16", "TC")
 
 
 # ---- refusals, each from the lowest refused stream -------------------------------------

@@ -15,10 +15,7 @@
 Every workload's outputs are checked equal (torch.equal).  Times are the
 median (min, max) of --steps repetitions after --warmup, wall clock between
 two device synchronisations; `device_ms` is the resident path between two
-events on the stream.  The resident path runs in its three variants
-(`Decoder.crop_variant`: codebook from global memory, codebook staged in LDS,
-unpack and synthesis fused), which is the A/B behind the default.  Prints one
-JSON line.
+events on the stream.  Prints one JSON line.
 """
 from __future__ import annotations
 
@@ -84,7 +81,6 @@ def main():
     n, ch, rate = st.samples_per_channel, st.channels, st.sample_rate
     dev = torch.device("cuda", st.device)
     rng = np.random.default_rng(2024)
-    default_variant = sc.Decoder.crop_variant()
 
     results = []
     for batch, secs in WORKLOADS:
@@ -123,26 +119,18 @@ def main():
             return torch.from_numpy(host).to(dev)
 
         row = {"crops": batch, "crop_seconds": secs, "crop_samples": T}
-        ab = {}
-        for variant in sc.Decoder.CROP_VARIANTS:
-            sc.Decoder.crop_variant(variant)
-            x, wall = timed(resident)
-            devs = sorted(device_ms() for _ in range(args.steps))
-            ab[variant] = {"wall_ms": wall,
-                           "device_ms": [round(statistics.median(devs), 4), round(devs[0], 4), round(devs[-1], 4)],
-                           "out": x}
-        sc.Decoder.crop_variant(default_variant)
         x, row["resident_ms"] = timed(resident)
+        devs = sorted(device_ms() for _ in range(args.steps))
+        row["device_ms"] = [round(statistics.median(devs), 4), round(devs[0], 4), round(devs[-1], 4)]
         row["h2d_bytes"] = sc.Decoder.last_timing()["h2d_bytes"]
         xf, row["resident_float32_ct_ms"] = timed(resident_float_ct)
         _, row["resident_enqueue_only_ms"] = timed(resident, sync=False)
         yp, row["parent_per_crop_ms"] = timed(parent_per_crop)
         yw, row["parent_whole_stream_ms"] = timed(parent_whole)
-        equal = bool(torch.equal(x, yp) and torch.equal(x, yw) and all(torch.equal(x, a.pop("out")) for a in ab.values()) and
+        equal = bool(torch.equal(x, yp) and torch.equal(x, yw) and
                      torch.equal(xf, (x.to(torch.float32) / 32768).transpose(1, 2).contiguous()))
         assert equal, f"outputs differ at {batch} crops of {secs} s"
         row["outputs_equal"] = equal
-        row["variant_ab"] = ab
         row["speedup_over_best_parent"] = round(min(row["parent_per_crop_ms"][0], row["parent_whole_stream_ms"][0]) /
                                                 row["resident_ms"][0], 1)
         results.append(row)
@@ -159,7 +147,7 @@ def main():
         "bench": "decode_crops", "config": "c2 -cs8 -cpf4096 -cbd8 44.1 kHz stereo", "seconds": args.seconds,
         "commit": commit, "gsc_bytes": len(gsc), "frames": st.frame_count,
         "checkpoint_symbols": sc.Decoder.checkpoint_symbols(), "steps": args.steps, "warmup": args.warmup,
-        "times": "[median, min, max] ms", "default_variant": default_variant,
+        "times": "[median, min, max] ms",
         "open_ms": round(open_ms, 2), "open_host_walk_ms": round(open_t["host_index_ms"], 2),
         "open_h2d_bytes": open_t["h2d_bytes"], "workloads": results,
     }

@@ -1,7 +1,6 @@
 // Stand-alone driver of the resampler's host side (gsc_resample.cpp, no HIP:
-// gsc::resample_shape, resample_table, plan_crops_fmt, which
-// gsc_decode_crops_fmt runs before it launches anything), meant for a host
-// sanitizer build:
+// gsc::resample_shape, resample_table, and plan_crops, which the crop calls
+// run before they launch anything), meant for a host sanitizer build:
 //   make -C soundchunks_amd/csrc resample_check
 //   soundchunks_amd/lib/decode_resample_check FILE.gsc...
 // Tables of six pairs of rates: shape, every row summing to 2^24, phase L - p
@@ -66,9 +65,9 @@ void check_plan(const gsc::Index& ix, int out_rate, const std::vector<gsc::Crop>
     const gsc::Index* ixs[1] = {&ix};
     gsc::CropPlan plan;
     std::string err;
-    const int rc = gsc::plan_crops_fmt(ixs, 1, crops.data(), int(crops.size()), length, out_rate, 0, &plan, &err);
+    const int rc = gsc::plan_crops(ixs, 1, crops.data(), int(crops.size()), length, out_rate, 0, &plan, &err);
     CHECK(rc == 0, "-> %d: plan refused: %s", out_rate, err.c_str());
-    CHECK(plan.crops.size() == crops.size() && plan.pieces.empty() && plan.channels == ix.channels, "plan shape");
+    CHECK(plan.crops.size() == crops.size() && plan.channels == ix.channels, "plan shape");
     const int g = std::gcd(ix.rate, out_rate);
     const int64_t L = out_rate / g, M = ix.rate / g, n = ix.samples;
     for (size_t ci = 0; ci < crops.size(); ++ci) {
@@ -103,7 +102,7 @@ void must_refuse(const std::vector<const gsc::Index*>& ixs, gsc::Crop c, int64_t
                  const char* what) {
     gsc::CropPlan plan;
     std::string err;
-    const int rc = gsc::plan_crops_fmt(ixs.data(), int(ixs.size()), &c, 1, length, rate, channels, &plan, &err);
+    const int rc = gsc::plan_crops(ixs.data(), int(ixs.size()), &c, 1, length, rate, channels, &plan, &err);
     CHECK(rc != 0 && !err.empty(), "%s accepted", what);
 }
 
@@ -177,7 +176,7 @@ int main(int argc, char** argv) {
         gsc::CropPlan plan;
         std::string err;
         gsc::Crop c{1, 0, 1};
-        if (gsc::plan_crops_fmt(ixs.data(), 2, &c, 1, 16, 44100, 1, &plan, &err) != 0 || plan.channels != 1) {
+        if (gsc::plan_crops(ixs.data(), 2, &c, 1, 16, 44100, 1, &plan, &err) != 0 || plan.channels != 1) {
             std::printf("FAIL: a mono output of %d and %d channels refused: %s\n", ca, cb, err.c_str());
             ++g_bad;
         }
