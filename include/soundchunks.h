@@ -588,6 +588,54 @@ int gsc_envelope_layout(const long long *samples, int n, int hop, long long *off
 int gsc_crop_binding_envelope(gsc_crop_binding *b, int hop, long long *energy_device, int *peak_device,
                               long long nblocks, void *hip_stream);
 
+/* ---- stream fidelity: block error energy of bound streams against source PCM ------ */
+/* How good an encode is, and where it is bad: per block and per stream the
+ * energy of the difference between what a resident stream decodes to and its
+ * source PCM, straight from the compressed slabs by one kernel launch; no PCM
+ * is written to memory.
+ *
+ * Definition.  A stream of S samples per channel and C channels decodes to
+ * int16 x[t][k], 0 <= t < S, 0 <= k < C, exactly as gsc_decode gives them.  Its
+ * reference is int16 r[t][k], interleaved [R, C] in device memory, with the
+ * stream's own C and at the stream's own rate: stream sample t corresponds to
+ * reference sample t.  R may be any value >= 0, and r[t][k] = 0 for t >= R.
+ * The encoder pads streams past their WAV, so S may exceed the source's length;
+ * reference samples at t >= S are ignored.  With d = x - r (|d| <= 65535),
+ * every block of a hop H has three results, hops and blocks being exactly
+ * those of gsc_envelope_layout (64 <= H <= 65536, block b covers samples
+ * [b H, min((b + 1) H, S)) of every channel, S = 0 gives no blocks) and the
+ * concatenation over streams the same:
+ *   err_energy[b] = sum of d^2 over the block's samples and all channels, as
+ *                   int64 (d^2 reaches 4,294,836,225: it does not fit a signed
+ *                   32-bit product);
+ *   ref_energy[b] = sum of r^2 over the same samples, as int64;
+ *   err_peak[b]   = max of |d| over the same samples, as int32.
+ * Every block of every stream is written.  Every sample of [0, S) contributes,
+ * including those that decode to zero.  A binding's out_rate and out_channels
+ * play no part.  All of it is integer arithmetic, so the results do not depend
+ * on the order of the sums.  The SNR of a block or a stream is 10 log10 of a
+ * sum of ref_energy over a sum of err_energy, which the caller forms.
+ *
+ * gsc_crop_binding_fidelity: ref_device and ref_samples are host arrays with
+ * one entry per bound stream: a device pointer to that stream's reference and
+ * the reference's samples per channel (R).  A null pointer with 0 samples is an
+ * all-zero reference.  References need no more than 2-byte alignment and are
+ * only read.  err_energy_device, ref_energy_device (int64) and err_peak_device
+ * (int32) are nblocks elements each in device memory; nblocks must equal the
+ * layout's total for the binding's streams.  A once-per-corpus call under
+ * gsc_crop_binding_envelope's licence: it may allocate, uploads its layout and
+ * the per-stream reference descriptors with a blocking copy, launches one
+ * kernel on hip_stream and waits for that stream before it returns.  A total
+ * of 0 blocks launches nothing.  Refused (-1 and gsc_last_error, the stream
+ * named where one is at fault): everything gsc_crop_binding_envelope refuses,
+ * null ref_device or ref_samples, a negative reference length, a null
+ * reference with a positive length, and a reference or an output that is not
+ * device memory of the binding's device.  The streams must still be open. */
+int gsc_crop_binding_fidelity(gsc_crop_binding *b, int hop, const void *const *ref_device,
+                              const long long *ref_samples, long long *err_energy_device,
+                              long long *ref_energy_device, int *err_peak_device, long long nblocks,
+                              void *hip_stream);
+
 /* Timing of the last gsc_decode*, gsc_stream_open or crop call on the calling
  * thread (milliseconds).  h2d_bytes: the bytes that call uploaded.  After
  * gsc_decode_crops or gsc_decode_crops_fmt h2d_bytes is the job descriptors

@@ -239,6 +239,9 @@ SIGNATURES = {
     "gsc_envelope_layout": (ctypes.c_int, [_LLP, ctypes.c_int, ctypes.c_int, _LLP]),
     "gsc_crop_binding_envelope": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
                                                  ctypes.c_longlong, ctypes.c_void_p]),
+    "gsc_crop_binding_fidelity": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p), _LLP,
+                                                 ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong,
+                                                 ctypes.c_void_p]),
     "gsc_crop_plan_model": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_longlong,
                                            ctypes.c_longlong, ctypes.c_longlong, ctypes.c_int, _LLP, _IP, _IP, _LLP,
                                            _LLP]),

@@ -305,6 +305,20 @@ std::string other_device(const std::string& what, int lives, int dev) {
            std::to_string(dev);
 }
 
+// 0, or `who`'s refusal of `what` at p, which is not device memory of device `dev` (where `owner` lives).
+// For once-per-corpus calls: it asks the runtime.
+int check_device_memory(const char* who, const std::string& what, const void* p, int dev, const char* owner) {
+    hipPointerAttribute_t at{};
+    const hipError_t e = hipPointerGetAttributes(&at, p);
+    if (e != hipSuccess) (void)hipGetLastError();
+    if (e != hipSuccess || (at.type != hipMemoryTypeDevice && at.type != hipMemoryTypeManaged))
+        return set_last_error(std::string(who) + ": " + what + " is not device memory");
+    if (at.type == hipMemoryTypeDevice && at.device != dev)
+        return set_last_error(std::string(who) + ": " + what + " lives on device " + std::to_string(at.device) +
+                              ", " + owner + " on device " + std::to_string(dev));
+    return 0;
+}
+
 // delete h on its own device, after the work queued there: crop calls still read what h owns
 template <typename Handle>
 void free_on_device(Handle* h) {
@@ -1144,16 +1158,9 @@ int gsc_crop_binding_envelope(gsc_crop_binding* b, int hop, long long* energy_de
         return set_last_error(other_device("gsc_crop_binding_envelope: the binding", b->device, dev));
     // once per corpus: the call may ask the runtime where its outputs live
     const std::pair<const void*, const char*> outs[2] = {{energy_device, "energy_device"}, {peak_device, "peak_device"}};
-    for (const auto& o : outs) {
-        hipPointerAttribute_t at{};
-        const hipError_t e = hipPointerGetAttributes(&at, o.first);
-        if (e != hipSuccess) (void)hipGetLastError();
-        if (e != hipSuccess || (at.type != hipMemoryTypeDevice && at.type != hipMemoryTypeManaged))
-            return set_last_error(std::string("gsc_crop_binding_envelope: ") + o.second + " is not device memory");
-        if (at.type == hipMemoryTypeDevice && at.device != b->device)
-            return set_last_error(std::string("gsc_crop_binding_envelope: ") + o.second + " lives on device " +
-                                  std::to_string(at.device) + ", the binding on device " + std::to_string(b->device));
-    }
+    for (const auto& o : outs)
+        if (check_device_memory("gsc_crop_binding_envelope", o.second, o.first, b->device, "the binding") != 0)
+            return -1;
     hipStream_t hs = static_cast<hipStream_t>(hip_stream);
     // The layout goes up as the binding's descriptors did: a blocking copy into memory of its own, which has
     // landed when the call launches on whatever stream; the call then waits for that stream before it frees it.
@@ -1162,6 +1169,58 @@ int gsc_crop_binding_envelope(gsc_crop_binding* b, int hop, long long* energy_de
     DEC_TRY(hipMemcpy(d_layout.p, layout.data(), layout.size() * sizeof(int64_t), hipMemcpyHostToDevice));
     DEC_TRY(gsc_launch_envelope(b->streams.p, n, d_layout.p, tile0[n], hop, reinterpret_cast<int64_t*>(energy_device),
                                 peak_device, nblocks, hs));
+    DEC_TRY(hipStreamSynchronize(hs));
+    return 0;
+}
+
+int gsc_crop_binding_fidelity(gsc_crop_binding* b, int hop, const void* const* ref_device,
+                              const long long* ref_samples, long long* err_energy_device,
+                              long long* ref_energy_device, int* err_peak_device, long long nblocks, void* hip_stream) {
+    const char* who = "gsc_crop_binding_fidelity";
+    if (!b) return set_last_error(std::string(who) + ": binding is null");
+    const int n = b->nstreams;
+    // one upload: tile0[n + 1] and block0[n + 1] as envelope_kernel reads them, then a FidelityRef per stream
+    const size_t nlayout = 2 * (size_t(n) + 1);
+    std::vector<int64_t> block(nlayout + 2 * size_t(n));
+    int64_t* tile0 = block.data();
+    int64_t* block0 = tile0 + n + 1;
+    std::vector<FidelityRef> refs(static_cast<size_t>(n));
+    std::string err;
+    if (envelope_layout(b->samples.data(), n, hop, block0, tile0, &err) != 0) return set_last_error(err);
+    if (nblocks != block0[n])
+        return set_last_error(std::string(who) + ": nblocks " + std::to_string(nblocks) + ", the binding's " +
+                              std::to_string(n) + " streams have " + std::to_string(block0[n]) + " blocks of " +
+                              std::to_string(hop) + " samples");
+    if (n > 0 && !ref_device) return set_last_error(std::string(who) + ": ref_device is null");
+    if (n > 0 && !ref_samples) return set_last_error(std::string(who) + ": ref_samples is null");
+    if (fidelity_refs(ref_device, reinterpret_cast<const int64_t*>(ref_samples), n, refs.data(), &err) != 0)
+        return set_last_error(err);
+    if (n == 0 || nblocks == 0) return 0;
+    std::memcpy(block.data() + nlayout, refs.data(), refs.size() * sizeof(FidelityRef));
+    const std::pair<const void*, const char*> outs[3] = {{err_energy_device, "err_energy_device"},
+                                                         {ref_energy_device, "ref_energy_device"},
+                                                         {err_peak_device, "err_peak_device"}};
+    for (const auto& o : outs)
+        if (!o.first) return set_last_error(std::string(who) + ": " + o.second + " is null");
+    int dev = 0;
+    DEC_TRY(hipGetDevice(&dev));
+    if (dev != b->device) return set_last_error(other_device(std::string(who) + ": the binding", b->device, dev));
+    // once per corpus: the call may ask the runtime where its outputs and its references live
+    for (const auto& o : outs)
+        if (check_device_memory(who, o.second, o.first, b->device, "the binding") != 0) return -1;
+    for (int i = 0; i < n; ++i)
+        if (refs[size_t(i)].pcm && check_device_memory(who, "stream " + std::to_string(i) + ": the reference",
+                                                       refs[size_t(i)].pcm, b->device, "the binding") != 0)
+            return -1;
+    hipStream_t hs = static_cast<hipStream_t>(hip_stream);
+    // as the envelope's layout: a blocking copy into memory of the call's own, freed after the stream's work
+    Dev<int64_t> d_block;
+    DEC_TRY(d_block.alloc(block.size()));
+    DEC_TRY(hipMemcpy(d_block.p, block.data(), block.size() * sizeof(int64_t), hipMemcpyHostToDevice));
+    DEC_TRY(gsc_launch_fidelity(b->streams.p, n, d_block.p, tile0[n],
+                                reinterpret_cast<const FidelityRef*>(d_block.p + nlayout), hop,
+                                reinterpret_cast<int64_t*>(err_energy_device),
+                                reinterpret_cast<int64_t*>(ref_energy_device), err_peak_device, nblocks, hs));
     DEC_TRY(hipStreamSynchronize(hs));
     return 0;
 }

@@ -3,19 +3,10 @@
 // has the definition).  No PCM is written to memory.
 //
 //   envelope_kernel   a workgroup of 256 lanes owns one tile of one stream, a
-//                     whole number of hops (envelope_tile_len, gsc_envelope.h),
-//                     so every block has one owner: nothing is combined across
-//                     workgroups and no global atomic is used.  Lane 0 finds the
-//                     stream and the tile from the call's layout (the first
-//                     workgroup and the first block of every stream), plans the
-//                     tile as a crop of the stream at its own rate
-//                     (crop_plan_one) and leaves the job in LDS, as the bound
-//                     crop kernels do.  The tile is then decoded as
-//                     crop_fused_kernel decodes it (fused_frame: per frame and
-//                     per stretch of checkpoint segments, unpack into LDS, then
-//                     table_sample with the codebook from global memory), but a
-//                     sample goes into a reduction where the crop kernels store
-//                     it.
+//                     whole number of hops, finds it with tile_plan and decodes
+//                     it with tile_walk (gsc_envelope_device.h, which
+//                     fidelity_kernel shares), and a sample goes into the
+//                     reduction below where the crop kernels store it.
 //
 // The reduction.  Consecutive lanes take consecutive elements (sample, channel)
 // of a run, so the 64 elements of a wave lie in at most two blocks (a hop is at
@@ -38,6 +29,7 @@
 #include "gsc_decode.h"
 #include "gsc_decode_device.h"
 #include "gsc_envelope.h"
+#include "gsc_envelope_device.h"
 #include "gsc_launch.h"
 
 namespace gsc {
@@ -93,12 +85,6 @@ __device__ __forceinline__ void envelope_run(int64_t ua, int64_t ub, int ch, int
     }
 }
 
-// where a workgroup's results go: blocks [first, first + count) of the output
-struct alignas(16) TilePlace {
-    int64_t first;
-    int32_t count, pad_;
-};
-
 // layout: tile0[nstreams + 1] (stream i's first workgroup), then block0[nstreams + 1] (its first block)
 __global__ __launch_bounds__(kFusedThreads) void envelope_kernel(const BoundStream* __restrict__ streams, int nstreams,
                                                                  const int64_t* __restrict__ layout, int hop,
@@ -119,32 +105,9 @@ __global__ __launch_bounds__(kFusedThreads) void envelope_kernel(const BoundStre
         acc_p[tid] = 0;
     }
     if (tid == 0) {
-        const int64_t* tile0 = layout;
-        const int64_t* block0 = layout + nstreams + 1;
-        const int64_t wg = blockIdx.x;
-        const int s = last_le(0, nstreams - 1, wg, [&](int i) { return tile0[i]; });
-        const int64_t tile = wg - tile0[s], ntiles = tile0[s + 1] - tile0[s];
-        const int64_t b0 = block0[s], nb = block0[s + 1] - b0;
-        CropJob j{};
-        TilePlace pl{0, 0, 0};
-        if (tile >= 0 && tile < ntiles && b0 >= 0 && nb > 0 && tile * bpt < nb) {
-            const int64_t left = nb - tile * bpt;
-            pl.first = b0 + tile * bpt;
-            pl.count = (int32_t)(left < bpt ? left : bpt);
-            const BoundStream& d = streams[s];
-            const ResFrame* frames = d.frames;
-            CropSpan sp;
-            // the tile as a crop of the stream at its own rate, whatever the binding's
-            if (d.channels > 0 && d.channels <= 255 &&
-                crop_plan_one(tile * tile_len, tile_len, tile_len, d.samples, d.nframes, 1, 1, 0,
-                              [&](int i) { return frames[i].first_sample; }, &sp) == kCropGood &&
-                sp.count > 0) {
-                j = CropJob{frames,     d.cps,   d.words,  d.cb,      d.att, d.ncp, d.nwords, d.ncb,
-                            d.natt,     tile * tile_len,   sp.count,  d.nframes,    sp.f0,    sp.f1,
-                            sp.src_begin,      sp.src_end, nullptr,     1,        1,
-                            0,          d.channels,        d.channels};
-            }
-        }
+        CropJob j;
+        TilePlace pl;
+        tile_plan(streams, nstreams, layout, hop, blockIdx.x, &j, &pl);
         sjob.job = j;
         splace = pl;
     }
@@ -153,30 +116,11 @@ __global__ __launch_bounds__(kFusedThreads) void envelope_kernel(const BoundStre
     const int64_t out_first = wave_uniform(splace.first);
     const int out_count = wave_uniform(splace.count);
     const int ch = job.src_ch;
-    const bool span_ok = job.f0 >= 0 && job.f0 < job.f1 && job.f1 <= job.nframes && ch > 0 && ch <= 255;
-    const int64_t tc = !span_ok ? 0 : (job.count < tile_len ? job.count : tile_len);
-    if (tc > 0) {
-        auto add = [&](int64_t ua, int64_t ub, auto value) {
-            if (ua < 0) ua = 0;
-            if (ub > tc) ub = tc;
-            if (ua < ub) envelope_run(ua, ub, ch, hop, bpt, acc_e, acc_p, tid, value);
-        };
-        auto frame = fused_frame(ssym, slut, tid);
-        // crop_walk_job's walk over the frames of [0, tc), without its zeros
-        const int fa = crop_frame_of(job, job.f0, job.f1, job.begin);
-        const int fb = crop_frame_of(job, job.f0, job.f1, job.begin + tc - 1);
-        int64_t done = 0;
-        for (int fr = fa; fr <= fb; ++fr) {
-            const ResFrame& f = job.frames[fr];
-            if (f.cs <= 0 || f.ch <= 0 || f.ch > 255 || f.count <= 0 || f.nsym <= 0) continue;
-            int64_t ta = f.first_sample - job.begin, tb = ta + f.nsym / f.ch * f.cs;
-            ta = ta < done ? done : ta;
-            tb = tb > tc ? tc : tb;
-            if (ta >= tb) continue;
-            frame(job, f, fr, ta, tb, add);
-            done = tb;
-        }
-    }
+    // the walk without its zeros: what no frame covers adds nothing to a sum of squares or a peak
+    tile_walk(
+        job, tile_samples(job, tile_len), ssym, slut, tid,
+        [&](int64_t ua, int64_t ub, auto value) { envelope_run(ua, ub, ch, hop, bpt, acc_e, acc_p, tid, value); },
+        [](int64_t, int64_t) {});
     __syncthreads();
     if (tid < out_count && tid < bpt) {
         const int64_t o = out_first + tid;

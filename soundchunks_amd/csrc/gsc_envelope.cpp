@@ -1,5 +1,5 @@
-// The block and workgroup layout of a stream envelope (gsc_envelope.h).  Host
-// only: no device, no HIP.
+// The block and workgroup layout of a stream envelope and the reference
+// descriptors of a fidelity call (gsc_envelope.h).  Host only: no device, no HIP.
 #include "gsc_envelope.h"
 
 namespace gsc {
@@ -29,6 +29,24 @@ int envelope_layout(const int64_t* samples, int n, int hop, int64_t* offsets, in
     }
     offsets[n] = blocks;
     if (tile0) tile0[n] = tiles;
+    return 0;
+}
+
+int fidelity_refs(const void* const* pcm, const int64_t* samples, int n, FidelityRef* out, std::string* err) {
+    auto fail = [&](const std::string& m) {
+        if (err) *err = m;
+        return -1;
+    };
+    if (n < 0 || (n > 0 && (!pcm || !samples || !out))) return fail("gsc fidelity: invalid argument");
+    for (int i = 0; i < n; ++i) {
+        if (samples[i] < 0)
+            return fail("gsc fidelity: stream " + std::to_string(i) + ": the reference has " +
+                        std::to_string(samples[i]) + " samples");
+        if (!pcm[i] && samples[i] > 0)
+            return fail("gsc fidelity: stream " + std::to_string(i) + ": the reference is null and has " +
+                        std::to_string(samples[i]) + " samples");
+        out[i] = FidelityRef{samples[i] > 0 ? static_cast<const int16_t*>(pcm[i]) : nullptr, samples[i]};
+    }
     return 0;
 }
 

@@ -1,7 +1,10 @@
-// Stream envelopes (include/soundchunks.h has the definition): how the blocks
-// of a binding's streams are laid out and how envelope_kernel
-// (gsc_decode_envelope.hip) splits them into workgroups, for the host and the
-// device alike.  tools/decode/envelope_check.cpp checks both without a device.
+// Stream envelopes and stream fidelity (include/soundchunks.h has the
+// definitions): how the blocks of a binding's streams are laid out and how
+// envelope_kernel (gsc_decode_envelope.hip) and fidelity_kernel
+// (gsc_decode_fidelity.hip) split them into workgroups, for the host and the
+// device alike, and the reference descriptors of a fidelity call.
+// tools/decode/envelope_check.cpp and fidelity_check.cpp check them without a
+// device.
 #pragma once
 #include <stdint.h>
 
@@ -31,5 +34,20 @@ GSC_HD constexpr int64_t envelope_tiles(int64_t nb, int hop) {
 // [kEnvelopeMinHop, kEnvelopeMaxHop], n < 0, a negative length and 2^31 or more
 // blocks in all.  Host only.
 int envelope_layout(const int64_t* samples, int n, int hop, int64_t* offsets, int64_t* tile0, std::string* err);
+
+// The reference of one stream of a fidelity call as fidelity_kernel reads it:
+// int16 [samples, channels of the stream] interleaved in device memory; null
+// with 0 samples is an all-zero reference.
+struct FidelityRef {
+    const int16_t* pcm;
+    int64_t samples;
+};
+static_assert(sizeof(FidelityRef) == 16, "two int64 of the call's upload per stream");
+
+// out[i] for n streams from the call's host arrays.  Refuses (-1, *err, the
+// stream named) a negative length and a null pointer with a positive length; a
+// pointer with 0 samples is kept as null, so that nothing can be read through
+// it.  Host only.
+int fidelity_refs(const void* const* pcm, const int64_t* samples, int n, FidelityRef* out, std::string* err);
 
 }  // namespace gsc

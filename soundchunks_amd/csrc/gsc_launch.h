@@ -23,6 +23,7 @@ struct ResFrame;
 struct TableSrc;
 struct CropJob;
 struct BoundStream;
+struct FidelityRef;  // gsc_envelope.h
 }  // namespace gsc
 
 extern "C" {
@@ -115,5 +116,10 @@ hipError_t gsc_prepare_crop_resample_bound(int src_samples);
 // ---- gsc_decode_envelope.hip
 hipError_t gsc_launch_envelope(const gsc::BoundStream* streams, int nstreams, const int64_t* layout, int64_t ntiles,
                                int hop, int64_t* energy, int32_t* peak, int64_t nblocks, hipStream_t st);
+
+// ---- gsc_decode_fidelity.hip
+hipError_t gsc_launch_fidelity(const gsc::BoundStream* streams, int nstreams, const int64_t* layout, int64_t ntiles,
+                               const gsc::FidelityRef* refs, int hop, int64_t* err_energy, int64_t* ref_energy,
+                               int32_t* err_peak, int64_t nblocks, hipStream_t st);
 
 }  // extern "C"

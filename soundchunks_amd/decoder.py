@@ -14,8 +14,10 @@ numpy.  ``Decoder.open_many(gscs, tables)`` opens a whole corpus as one
 describes streams once on the device (``CropBinding``), whose ``decode_crops``
 takes the crops from a device tensor, and whose ``envelope`` gives the block
 energy and peak of every bound stream (``Envelope``), from which
-``Envelope.sample_crops`` draws crops where there is sound.  torch is imported
-by the crop and envelope calls alone.
+``Envelope.sample_crops`` draws crops where there is sound, and whose
+``fidelity`` gives the block error energy of every bound stream against its
+source PCM (``Fidelity``).  torch is imported by the crop, envelope and fidelity
+calls alone.
 """
 from __future__ import annotations
 
@@ -186,6 +188,10 @@ class ResidentStream:
         """``Decoder.envelope([self], hop)``."""
         return Decoder.envelope([self], hop)
 
+    def fidelity(self, ref, hop: int = 1024) -> "Fidelity":
+        """``Decoder.fidelity([self], [ref], hop)``."""
+        return Decoder.fidelity([self], [ref], hop)
+
     def _handle(self):
         if not getattr(self, "_h", None):
             raise _lib.GscError("the resident stream is closed")
@@ -269,6 +275,10 @@ class StreamSet:
     def envelope(self, hop: int = 1024) -> "Envelope":
         """``Decoder.envelope(self.streams, hop)``: stream indices count the set's members."""
         return Decoder.envelope(self.streams, hop)
+
+    def fidelity(self, refs, hop: int = 1024) -> "Fidelity":
+        """``Decoder.fidelity(self.streams, refs, hop)``: stream indices count the set's members."""
+        return Decoder.fidelity(self.streams, refs, hop)
 
     def close(self) -> None:
         if getattr(self, "_h", None):
@@ -394,34 +404,110 @@ class CropBinding:
         write into."""
         import torch
 
-        if not getattr(self, "_h", None):
-            raise _lib.GscError("the crop binding is closed")
-        for o in self._owners:
-            if not getattr(o, "_h", None):
-                raise _lib.GscError("a stream of the crop binding is closed")
+        self._check_open()
         device = self.device
         hop = int(hop)
         samples = [int(s.samples_per_channel) for s in self._streams]
         channels = [int(s.channels) for s in self._streams]
         offsets = Decoder.envelope_layout(samples, hop)
         total = offsets[-1]
-        made = []
-        for name, t, dt in (("energy", energy, torch.int64), ("peak", peak, torch.int32)):
-            if t is None:
-                t = torch.empty((total,), dtype=dt, device=device)
-            elif not isinstance(t, torch.Tensor) or t.device != device:
-                where = t.device if isinstance(t, torch.Tensor) else type(t).__name__
-                raise _lib.GscError(f"envelope: {name} must be a tensor on {device}, got {where}")
-            elif t.dtype != dt or tuple(t.shape) != (total,) or not t.is_contiguous():
-                raise _lib.GscError(f"envelope: {name} must be a contiguous {dt} tensor [{total}], got {t.dtype} "
-                                    f"{tuple(t.shape)}")
-            made.append(t)
-        energy, peak = made
+        energy, peak = self._block_outputs("envelope", total, (("energy", energy, torch.int64),
+                                                               ("peak", peak, torch.int32)))
         with torch.cuda.device(device):
             hip_stream = ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
             _lib.check(_lib.load().gsc_crop_binding_envelope(self._h, hop, energy.data_ptr(), peak.data_ptr(), total,
                                                              hip_stream))
         return Envelope(hop, samples, channels, offsets, energy, peak)
+
+    def fidelity(self, refs, hop: int = 1024, err_energy=None, ref_energy=None, err_peak=None) -> "Fidelity":
+        """Block error energy of every bound stream against its source PCM
+        (include/soundchunks.h has the definition): per block of ``hop`` source
+        samples (the envelope's blocks) of a stream, all channels, the sum of
+        ``(decoded - reference)**2`` and of ``reference**2`` as ``torch.int64``
+        and the largest ``|decoded - reference|`` as ``torch.int32``.  ``refs``
+        has one entry per stream: a contiguous ``torch.int16`` tensor ``[R, C]``
+        on the streams' device, read in place, or a numpy int16 ``[R, C]``
+        array, which the call uploads; ``C`` is the stream's channel count,
+        sample t of the reference is sample t of the stream, ``R`` may be
+        anything: the reference is zero past its end and ignored past the
+        stream's.  One kernel launch on torch's current stream, straight from
+        the compressed slabs; the binding's ``rate`` and ``channels`` play no
+        part.  A once-per-corpus call, as ``envelope``: it allocates, copies and
+        waits for the stream.  ``err_energy`` / ``ref_energy`` / ``err_peak``:
+        contiguous tensors of the layout's total on the streams' device to
+        write into."""
+        import torch
+
+        self._check_open()
+        device = self.device
+        hop = int(hop)
+        refs = list(refs)
+        n = len(self._streams)
+        if len(refs) != n:
+            raise _lib.GscError(f"fidelity: {len(refs)} references for {n} streams")
+        held = []  # the references as device tensors, alive until the call has waited for its stream
+        for i, (r, st) in enumerate(zip(refs, self._streams)):
+            ch = int(st.channels)
+            if isinstance(r, np.ndarray):
+                dtype_ok, contiguous = r.dtype == np.int16, r.flags.c_contiguous
+            elif isinstance(r, torch.Tensor):
+                dtype_ok, contiguous = r.dtype == torch.int16, r.is_contiguous()
+            else:
+                raise _lib.GscError(f"fidelity: reference {i} is {type(r).__name__}, neither a torch tensor nor a "
+                                    f"numpy array")
+            if not dtype_ok:
+                raise _lib.GscError(f"fidelity: reference {i} must be int16, got {r.dtype}")
+            if r.ndim != 2 or r.shape[1] != ch:
+                raise _lib.GscError(f"fidelity: reference {i} must be [R, {ch}], stream {i} has {ch} channels, got "
+                                    f"{tuple(r.shape)}")
+            if not contiguous:
+                raise _lib.GscError(f"fidelity: reference {i} is not contiguous")
+            if isinstance(r, np.ndarray):
+                r = torch.from_numpy(r if r.flags.writeable else r.copy()).to(device)
+            elif r.device != device:
+                raise _lib.GscError(f"fidelity: reference {i} is on {r.device}, the streams live on {device}")
+            held.append(r)
+        samples = [int(s.samples_per_channel) for s in self._streams]
+        channels = [int(s.channels) for s in self._streams]
+        offsets = Decoder.envelope_layout(samples, hop)
+        total = offsets[-1]
+        err_energy, ref_energy, err_peak = self._block_outputs(
+            "fidelity", total, (("err_energy", err_energy, torch.int64), ("ref_energy", ref_energy, torch.int64),
+                                ("err_peak", err_peak, torch.int32)))
+        ptrs = (ctypes.c_void_p * n)(*[r.data_ptr() if r.numel() else None for r in held])
+        lens = (ctypes.c_longlong * n)(*[int(r.shape[0]) for r in held])
+        with torch.cuda.device(device):
+            hip_stream = ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+            _lib.check(_lib.load().gsc_crop_binding_fidelity(self._h, hop, ptrs, lens, err_energy.data_ptr(),
+                                                             ref_energy.data_ptr(), err_peak.data_ptr(), total,
+                                                             hip_stream))
+        del held
+        return Fidelity(hop, samples, channels, offsets, err_energy, ref_energy, err_peak)
+
+    def _check_open(self):
+        if not getattr(self, "_h", None):
+            raise _lib.GscError("the crop binding is closed")
+        for o in self._owners:
+            if not getattr(o, "_h", None):
+                raise _lib.GscError("a stream of the crop binding is closed")
+
+    def _block_outputs(self, who, total, wanted):
+        """The per-block outputs of ``who``: (name, given tensor or None, dtype) each, made where not given."""
+        import torch
+
+        device = self.device
+        made = []
+        for name, t, dt in wanted:
+            if t is None:
+                t = torch.empty((total,), dtype=dt, device=device)
+            elif not isinstance(t, torch.Tensor) or t.device != device:
+                where = t.device if isinstance(t, torch.Tensor) else type(t).__name__
+                raise _lib.GscError(f"{who}: {name} must be a tensor on {device}, got {where}")
+            elif t.dtype != dt or tuple(t.shape) != (total,) or not t.is_contiguous():
+                raise _lib.GscError(f"{who}: {name} must be a contiguous {dt} tensor [{total}], got {t.dtype} "
+                                    f"{tuple(t.shape)}")
+            made.append(t)
+        return made
 
     @staticmethod
     def last_call() -> dict:
@@ -442,22 +528,18 @@ class CropBinding:
             pass
 
 
-class Envelope:
-    """Block energy and peak of the streams of a binding
-    (``CropBinding.envelope``).  ``hop``; ``samples`` and ``channels`` per stream
-    (host lists); ``offsets``: ``torch.int64`` [n + 1] on the device, stream i's
-    first block, and ``offsets_host``, the same as a list; ``energy``
-    ``torch.int64`` [total] and ``peak`` ``torch.int32`` [total] on the device.
-    It owns plain tensors, so it outlives the binding and the streams."""
+class _Blocks:
+    """The blocks of ``hop`` samples of several streams back to back
+    (``Decoder.envelope_layout``): ``hop``; ``samples`` and ``channels`` per
+    stream (host lists); ``offsets``: ``torch.int64`` [n + 1] on ``device``,
+    stream i's first block, and ``offsets_host``, the same as a list."""
 
-    def __init__(self, hop, samples, channels, offsets_host, energy, peak):
+    def __init__(self, hop, samples, channels, offsets_host, device):
         import torch
 
         self.hop = int(hop)
         self.samples, self.channels = list(samples), list(channels)
         self.offsets_host = list(offsets_host)
-        self.energy, self.peak = energy, peak
-        device = energy.device
         i64 = dict(dtype=torch.int64, device=device)
         self.offsets = torch.tensor(self.offsets_host, **i64)
         self._samples = torch.tensor(self.samples, **i64).reshape(-1)
@@ -472,10 +554,26 @@ class Envelope:
     def __len__(self) -> int:
         return self.offsets_host[-1]
 
+    def _range(self, i: int):
+        i = range(len(self.samples))[i]
+        return self.offsets_host[i], self.offsets_host[i + 1]
+
+
+class Envelope(_Blocks):
+    """Block energy and peak of the streams of a binding
+    (``CropBinding.envelope``).  ``hop``; ``samples`` and ``channels`` per stream
+    (host lists); ``offsets``: ``torch.int64`` [n + 1] on the device, stream i's
+    first block, and ``offsets_host``, the same as a list; ``energy``
+    ``torch.int64`` [total] and ``peak`` ``torch.int32`` [total] on the device.
+    It owns plain tensors, so it outlives the binding and the streams."""
+
+    def __init__(self, hop, samples, channels, offsets_host, energy, peak):
+        super().__init__(hop, samples, channels, offsets_host, energy.device)
+        self.energy, self.peak = energy, peak
+
     def blocks(self, i: int):
         """(energy, peak) of stream i: views of its blocks."""
-        i = range(len(self.samples))[i]
-        a, b = self.offsets_host[i], self.offsets_host[i + 1]
+        a, b = self._range(i)
         return self.energy[a:b], self.peak[a:b]
 
     def active(self, min_rms=None, min_peak=None):
@@ -540,6 +638,69 @@ class Envelope:
         out[:, 1] = torch.where(some, begin, 0)
         out[:, 2] = count
         return out
+
+
+class Fidelity(_Blocks):
+    """Block error energy of the streams of a binding against their source PCM
+    (``CropBinding.fidelity``).  ``hop``, ``samples``, ``channels``, ``offsets``
+    and ``offsets_host`` as ``Envelope`` has them; ``err_energy`` and
+    ``ref_energy`` ``torch.int64`` [total], ``err_peak`` ``torch.int32``
+    [total].  It owns plain tensors, so it outlives the binding and the
+    streams.  Its methods are torch ops on the tensors' device and synchronise
+    nothing; they work on CPU tensors too."""
+
+    def __init__(self, hop, samples, channels, offsets_host, err_energy, ref_energy, err_peak):
+        super().__init__(hop, samples, channels, offsets_host, err_energy.device)
+        self.err_energy, self.ref_energy, self.err_peak = err_energy, ref_energy, err_peak
+
+    def blocks(self, i: int):
+        """(err_energy, ref_energy, err_peak) of stream i: views of its blocks."""
+        a, b = self._range(i)
+        return self.err_energy[a:b], self.ref_energy[a:b], self.err_peak[a:b]
+
+    @staticmethod
+    def _snr_db(ref, err):
+        import torch
+
+        # 0 / x is 0 and log10(0) is -inf; x / 0 and 0 / 0 are replaced: no error is +inf whatever the reference
+        ratio = ref.to(torch.float64) / err.to(torch.float64)
+        return torch.where(err == 0, torch.full_like(ratio, float("inf")), 10.0 * torch.log10(ratio))
+
+    def snr_db(self):
+        """``torch.float64`` [total]: ``10 * log10(ref_energy / err_energy)`` per
+        block; ``+inf`` where the error is 0, ``-inf`` where only the reference is."""
+        return self._snr_db(self.ref_energy, self.err_energy)
+
+    def stream_sums(self):
+        """(err_energy, ref_energy) summed over each stream's blocks: exact ``torch.int64`` [n]."""
+        import torch
+
+        def per_stream(x):
+            c = torch.cat([x.new_zeros(1), torch.cumsum(x, 0)])
+            return c[self.offsets[1:]] - c[self.offsets[:-1]]
+
+        return per_stream(self.err_energy), per_stream(self.ref_energy)
+
+    def stream_snr_db(self):
+        """``torch.float64`` [n]: the SNR of each whole stream, from the exact
+        int64 sums over its blocks; the infinities as in ``snr_db`` (a stream
+        without samples has no error: ``+inf``)."""
+        err, ref = self.stream_sums()
+        return self._snr_db(ref, err)
+
+    def worst(self, k: int):
+        """The ``min(k, total)`` blocks with the lowest SNR, lowest first, equal
+        ones in block order: ``(stream, first_sample, snr_db)``, ``torch.int64``,
+        ``torch.int64`` and ``torch.float64`` [k].  ``first_sample`` is the
+        block's first sample in its stream."""
+        import torch
+
+        k = int(k)
+        if k < 0:
+            raise _lib.GscError(f"worst: k {k}")
+        snr, order = torch.sort(self.snr_db(), stable=True)
+        order = order[:k]
+        return self._stream[order], self._first[order], snr[:k]
 
 
 def wav_header(channels: int, rate: int, size: int) -> bytes:
@@ -710,6 +871,18 @@ class Decoder:
         b = CropBinding(streams)
         try:
             return b.envelope(hop)
+        finally:
+            b.close()
+
+    @staticmethod
+    def fidelity(streams, refs, hop: int = 1024) -> Fidelity:
+        """The fidelity of resident streams against ``refs``, one per stream:
+        binds them for the call (``rate=None, channels=None``, so their channel
+        counts must agree), runs ``CropBinding.fidelity`` and closes the binding
+        again."""
+        b = CropBinding(streams)
+        try:
+            return b.fidelity(refs, hop)
         finally:
             b.close()
 
