@@ -549,6 +549,58 @@ int gsc_crop_plan_model(const gsc_index *ix, int nstreams, int stream, long long
                         long long length, int out_rate, long long *written, int *f0, int *f1, long long *src_begin,
                         long long *src_end);
 
+/* ---- mixing crops: gain-weighted sums of crops of bound streams ------------------- */
+/* Noise and reverb augmentation, overlapped speakers, "speech + music + noise":
+ * every output row is a weighted sum of several crops.  gsc_crop_binding_mix
+ * forms the rows in one kernel launch straight from the resident compressed
+ * slabs; no source's PCM and no intermediate row is written to memory.
+ *
+ * Definition.  A source is {stream, begin, count, gain}, all int64.  stream,
+ * begin and count are exactly a crop of gsc_crop_binding_decode: the same units
+ * (begin in source samples of the stream, count and length in output samples at
+ * the binding's rate), the same clipping at the stream's end, the same
+ * conversion to the binding's out_rate and out_channels.  gain is Q15: 32768 is
+ * unity, -32768 inverts; -2^20 <= gain <= 2^20.  With x_k[t][c] the int16 value
+ * gsc_crop_binding_decode would write for source k at output sample t and
+ * channel c (zero at and after the source's clipped count), row r with sources
+ * k = 0 .. nsrc - 1 is
+ *   s       = sum over k of gain_k * x_k[t][c]            exact, in 64 bits
+ *   y[t][c] = clamp((s + 16384) >> 15, -32768, 32767)     arithmetic shift: floor
+ * int16 output is y, float32 output y / 32768 (exact), the relation of
+ * gsc_decode_crops.  |s| stays below 2^43.  written[r] is the largest clipped
+ * count among the row's sources, 0 when all are empty; elements at or past
+ * every source's clipped count are 0, and the whole length of every row is
+ * written.  A slot with count == 0 adds nothing and reads no stream data: that
+ * is how a row uses fewer than nsrc sources (its stream, begin and gain must
+ * still be valid).
+ *
+ * Bad rows.  A row is bad when one of its sources is a bad crop by
+ * gsc_crop_binding_decode's rules (stream outside the binding, begin < 0 or
+ * past the stream's samples, count < 0 or > length) or has a gain outside
+ * [-2^20, 2^20].  A bad row is zero over its whole length, written[r] is -1,
+ * and every other row is what it would be without it.
+ *
+ * gsc_crop_binding_mix.  sources_device is nrows x nsrc x {stream, begin,
+ * count, gain}, contiguous int64 in device memory; 1 <= nsrc <= 256.
+ * dst_device, dtype, layout and written_device (nrows int64, may be NULL) are
+ * gsc_crop_binding_decode's, and so is the call contract: the call reads no
+ * source on the host, allocates nothing, copies nothing, synchronises nothing
+ * and keeps no scratch between calls; it checks dtype, layout, the pointers,
+ * nsrc, that nrows x length x channels and length x the largest decimation step
+ * stay within 2^40 and that the calling thread is on the binding's device, and
+ * launches one kernel on hip_stream; nrows == 0 or length == 0 launches nothing
+ * and leaves written_device as it is.  Everything is ordered with hip_stream
+ * alone.  gsc_crop_binding_last_call reports the calling thread's last
+ * gsc_crop_binding_decode or gsc_crop_binding_mix.
+ *
+ * gsc_mix_model: the arithmetic alone, on the host and without a device (parity
+ * tests): *y from n pairs (x[i], gain[i]), 1 <= n <= 256.  Returns 0, or -1 for
+ * a null pointer, another n or a gain outside the range (nothing is written). */
+int gsc_crop_binding_mix(gsc_crop_binding *b, const long long *sources_device, int nrows, int nsrc, int dtype,
+                         int layout, long long length, void *dst_device, long long *written_device,
+                         void *hip_stream);
+int gsc_mix_model(const int16_t *x, const long long *gain, int n, int16_t *y);
+
 /* ---- stream envelopes: block energy and peak of bound streams -------------------- */
 /* A sampler that draws crops on the device needs to know where a stream holds
  * sound.  The envelope of a stream is computed straight from its resident

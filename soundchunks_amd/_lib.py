@@ -234,6 +234,10 @@ SIGNATURES = {
     "gsc_crop_binding_decode": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
                                                ctypes.c_int, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_void_p,
                                                ctypes.c_void_p]),
+    "gsc_crop_binding_mix": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                            ctypes.c_int, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_void_p,
+                                            ctypes.c_void_p]),
+    "gsc_mix_model": (ctypes.c_int, [_I16P, _LLP, ctypes.c_int, _I16P]),
     "gsc_crop_binding_last_call": (None, [ctypes.POINTER(GscCropCallStats)]),
     "gsc_crop_binding_free": (None, [ctypes.c_void_p]),
     "gsc_envelope_layout": (ctypes.c_int, [_LLP, ctypes.c_int, ctypes.c_int, _LLP]),

@@ -31,6 +31,7 @@
 #include "gsc_envelope.h"
 #include "gsc_hip_host.h"
 #include "gsc_launch.h"
+#include "gsc_mix.h"
 
 struct gsc_index {
     gsc::Index ix;
@@ -382,7 +383,7 @@ struct BoundShape {
     }
 };
 
-thread_local gsc_crop_call_stats t_bstat;  // the last gsc_crop_binding_decode
+thread_local gsc_crop_call_stats t_bstat;  // the last gsc_crop_binding_decode or gsc_crop_binding_mix
 
 }  // namespace
 }  // namespace gsc
@@ -1081,7 +1082,10 @@ gsc_crop_binding* gsc_crop_binding_create(gsc_stream* const* streams, int nstrea
     if (hip_failed(b->streams.alloc(desc.size()), "hipMalloc") ||
         hip_failed(hipMemcpy(b->streams.p, desc.data(), desc.size() * sizeof(BoundStream), hipMemcpyHostToDevice),
                    "hipMemcpy") ||
-        (b->fmt && hip_failed(gsc_prepare_crop_resample_bound(b->src_samples(kResampleTile)), "LDS limit")))
+        (b->fmt && hip_failed(gsc_prepare_crop_resample_bound(b->src_samples(kResampleTile)), "LDS limit")) ||
+        (b->fmt && hip_failed(gsc_prepare_crop_mix(b->channels,
+                                                   b->src_samples(mix_tile_len(b->channels, kResampleTile))),
+                              "LDS limit")))
         return nullptr;
     return b.release();
 }
@@ -1116,6 +1120,38 @@ int gsc_crop_binding_decode(gsc_crop_binding* b, const long long* crops_device, 
             DEC_TRY(gsc_launch_crop_fused_bound(b->streams.p, b->nstreams, crops, ncrops, length, C, is_float, planar,
                                                 int(std::min<int64_t>(length, kCropTile)), dst_device, written, hs));
         }
+        ++stats.launches;
+    }
+    stats.host_ms = now_ms() - t_begin;
+    return 0;
+}
+
+int gsc_crop_binding_mix(gsc_crop_binding* b, const long long* sources_device, int nrows, int nsrc, int dtype,
+                         int layout, long long length, void* dst_device, long long* written_device,
+                         void* hip_stream) {
+    const double t_begin = now_ms();
+    gsc_crop_call_stats& stats = t_bstat = gsc_crop_call_stats{};
+    if (!b) return set_last_error("gsc_crop_binding_mix: binding is null");
+    if (check_pcm_format("gsc_crop_binding_mix", dtype, layout) != 0) return -1;
+    if (nrows < 0 || length < 0) return set_last_error("gsc_crop_binding_mix: invalid argument");
+    if (nsrc < 1 || nsrc > kMixMaxSources)
+        return set_last_error("gsc_crop_binding_mix: " + std::to_string(nsrc) + " sources per row, 1 to " +
+                              std::to_string(kMixMaxSources) + " are possible");
+    if (nrows > 0 && length > 0) {
+        if (!sources_device) return set_last_error("gsc_crop_binding_mix: sources_device is null");
+        if (!dst_device) return set_last_error("gsc_crop_binding_mix: dst_device is null");
+        const int C = b->channels;
+        if (length > (int64_t(1) << 40) / (int64_t(nrows) * C) || length > (int64_t(1) << 40) / b->max_step)
+            return set_last_error("gsc_crop_binding_mix: output too large for one call");
+        int dev = 0;
+        DEC_TRY(hipGetDevice(&dev));
+        if (dev != b->device) return set_last_error(other_device("gsc_crop_binding_mix: the binding", b->device, dev));
+        // the launch shape comes from the binding alone: no source is read here
+        const int64_t tile = std::min<int64_t>(length, mix_tile_len(C, kResampleTile));
+        DEC_TRY(gsc_launch_crop_mix(b->streams.p, b->nstreams, reinterpret_cast<const int64_t*>(sources_device), nrows,
+                                    nsrc, length, C, dtype == GSC_PCM_FLOAT32, layout == GSC_LAYOUT_CT, b->fmt,
+                                    b->fmt ? b->src_samples(tile) : 0, dst_device,
+                                    reinterpret_cast<int64_t*>(written_device), static_cast<hipStream_t>(hip_stream)));
         ++stats.launches;
     }
     stats.host_ms = now_ms() - t_begin;

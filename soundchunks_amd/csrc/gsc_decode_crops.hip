@@ -38,12 +38,10 @@
 namespace gsc {
 namespace {
 
-// The walk of both kernels.  A workgroup owns samples [t0, t1) of one
-// crop's row, every channel: [t0, tc) are decoded, [tc, t1) lie past the
-// crop's clipped length and are zeroed.  The frames that [t0, tc) crosses are
-// taken one after another: frame(job, f, fr, ta, tb, write) writes the frame's
-// share [ta, tb) with write(ua, ub, value), and puts its own barriers around
-// what it keeps in LDS.  What no frame of a stale span covers is zeroed too.
+// The walk of both kernels (crop_walk_run, gsc_decode_device.h) with a sink that
+// stores: a workgroup owns samples [t0, t1) of one crop's row, every channel;
+// what lies past the crop's clipped length and what no frame of a stale span
+// covers is zeroed.
 template <typename T, bool PLANAR, typename Frame>
 __device__ __forceinline__ void crop_walk_job(const CropJob& job, int64_t crop, int64_t tile, int64_t length,
                                               int channels, int tile_len, T* __restrict__ out, int64_t nout,
@@ -51,32 +49,13 @@ __device__ __forceinline__ void crop_walk_job(const CropJob& job, int64_t crop, 
     const int64_t t0 = tile * tile_len;
     const int64_t t1 = t0 + tile_len < length ? t0 + tile_len : length;
     if (t0 >= t1) return;
-    const bool span_ok = job.f0 >= 0 && job.f0 < job.f1 && job.f1 <= job.nframes;
-    const int64_t tc = !span_ok ? t0 : (job.count < t1 ? (job.count > t0 ? job.count : t0) : t1);
     const int64_t out_base = crop * length * channels;
     const int tid = threadIdx.x;
     auto write = [&](int64_t ua, int64_t ub, auto value) {
         crop_write_run<T, PLANAR>(ua, ub, channels, length, out_base, out, nout, tid, kFusedThreads, value);
     };
-    auto zero = [](int64_t, int) { return (int16_t)0; };
-    write(tc, t1, zero);
-    if (tc <= t0) return;
-    const int fa = crop_frame_of(job, job.f0, job.f1, job.begin + t0);
-    const int fb = crop_frame_of(job, job.f0, job.f1, job.begin + tc - 1);
-    int64_t done = t0;  // every sample of [t0, done) is written
-    for (int fr = fa; fr <= fb; ++fr) {
-        const ResFrame& f = job.frames[fr];
-        if (f.cs <= 0 || f.ch <= 0 || f.ch > 255 || f.count <= 0 || f.nsym <= 0) continue;
-        // this frame's share of the run
-        int64_t ta = f.first_sample - job.begin, tb = ta + f.nsym / f.ch * f.cs;
-        ta = ta < done ? done : ta;
-        tb = tb > tc ? tc : tb;
-        if (ta >= tb) continue;
-        write(done, ta, zero);
-        frame(job, f, fr, ta, tb, write);
-        done = tb;
-    }
-    write(done, tc, zero);
+    auto blank = [&](int64_t ua, int64_t ub) { write(ua, ub, [](int64_t, int) { return (int16_t)0; }); };
+    crop_walk_run(job, t0, t1, write, blank, frame);
 }
 
 // A workgroup: tile blockIdx.x % tiles of crop blockIdx.x / tiles, whose job the

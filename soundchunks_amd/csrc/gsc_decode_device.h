@@ -1,9 +1,10 @@
 // What the decode kernels and their launchers share (gsc_decode.hip,
-// gsc_decode_crops.hip, gsc_decode_resample.hip), each in one place: the bit
+// gsc_decode_crops.hip, gsc_decode_resample.hip, gsc_decode_mix.hip), each in one place: the bit
 // walk of one checkpoint segment and the sample arithmetic
 // (decoder/decoder.lpr:163-203), the binary search, a frame's tables staged in
 // LDS or read from global memory, a crop's segments, frames and output
-// elements, the job of a crop that is planned on the device, and the
+// elements, the walk of a crop's frames and the passes of a resampled tile with
+// the caller's sink, the job of a crop that is planned on the device, and the
 // dynamic-LDS limit.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -236,6 +237,40 @@ __device__ __forceinline__ void crop_write_run(int64_t ta, int64_t tb, int chann
     }
 }
 
+// The walk of the native-rate crop kernels (crop_fused_kernel,
+// crop_fused_bound_kernel, mix_fused_kernel).  A workgroup owns samples
+// [t0, t1) of one crop's row, every channel: [t0, tc) are decoded, [tc, t1) lie
+// past the crop's clipped length.  The frames that [t0, tc) crosses are taken
+// one after another: frame(job, f, fr, ta, tb, write) hands the frame's share
+// [ta, tb) to write(ua, ub, value) and puts its own barriers around what it
+// keeps in LDS.  blank(ua, ub) gets what is past the clipped length and what no
+// frame of a stale span covers.  write and blank are the caller's sink: the crop
+// kernels store, the mix kernels accumulate.
+template <typename Write, typename Blank, typename Frame>
+__device__ __forceinline__ void crop_walk_run(const CropJob& job, int64_t t0, int64_t t1, Write write, Blank blank,
+                                              Frame frame) {
+    const bool span_ok = job.f0 >= 0 && job.f0 < job.f1 && job.f1 <= job.nframes;
+    const int64_t tc = !span_ok ? t0 : (job.count < t1 ? (job.count > t0 ? job.count : t0) : t1);
+    blank(tc, t1);
+    if (tc <= t0) return;
+    const int fa = crop_frame_of(job, job.f0, job.f1, job.begin + t0);
+    const int fb = crop_frame_of(job, job.f0, job.f1, job.begin + tc - 1);
+    int64_t done = t0;  // every sample of [t0, done) is written
+    for (int fr = fa; fr <= fb; ++fr) {
+        const ResFrame& f = job.frames[fr];
+        if (f.cs <= 0 || f.ch <= 0 || f.ch > 255 || f.count <= 0 || f.nsym <= 0) continue;
+        // this frame's share of the run
+        int64_t ta = f.first_sample - job.begin, tb = ta + f.nsym / f.ch * f.cs;
+        ta = ta < done ? done : ta;
+        tb = tb > tc ? tc : tb;
+        if (ta >= tb) continue;
+        blank(done, ta);
+        frame(job, f, fr, ta, tb, write);
+        done = tb;
+    }
+    blank(done, tc);
+}
+
 // ---- the fused walk of a frame (crop_fused_kernel, crop_fused_bound_kernel, envelope_kernel) ----
 
 // No symbol scratch and no unpack launch.  A workgroup takes a run of tile_len
@@ -378,6 +413,130 @@ __device__ __forceinline__ CropJob bound_job(const BoundStream* __restrict__ str
     __syncthreads();
     return shared_job_load(sjob);
 }
+
+// ---- the resampling crop kernels (gsc_decode_resample.hip, gsc_decode_mix.hip) ----
+
+constexpr int kResThreads = 256;
+constexpr int kResSegs = 16;  // checkpoint segments of one stretch in LDS
+
+// Samples [sa, sb) of a crop's stream, every channel, to
+// ssrc[(s - ia) * ch + k], by a whole workgroup; what no frame covers stays as it is.
+__device__ __forceinline__ void resample_fill(const CropJob& job, int64_t sa, int64_t sb, int64_t ia, int ch,
+                                              int16_t* ssrc, int src_cap, uint16_t* ssym, int* slut, int tid) {
+    const TableSlabs g = crop_tables(job);
+    const int fa = crop_frame_of(job, job.f0, job.f1, sa);
+    const int fb = crop_frame_of(job, job.f0, job.f1, sb - 1);
+    for (int fr = fa; fr <= fb; ++fr) {
+        const ResFrame& f = job.frames[fr];
+        if (f.cs <= 0 || f.ch != ch || f.count <= 0 || f.nsym <= 0) continue;
+        const int cs = f.cs;
+        const int64_t fs = f.first_sample, fe = fs + f.nsym / ch * cs;
+        const int64_t xa = sa > fs ? sa : fs, xb = sb < fe ? sb : fe;
+        if (xa >= xb) continue;
+        const int64_t qa = (xa - fs) / cs, qb = (xb - 1 - fs) / cs;
+        // rows per stretch: their symbols span at most kResSegs segments wherever the stretch starts
+        const int64_t rows = (int64_t)(kResSegs - 1) * kDecodeS / ch;
+        for (int64_t q0 = qa; q0 <= qb; q0 += rows) {
+            const int64_t q1 = q0 + rows - 1 < qb ? q0 + rows - 1 : qb;
+            const int64_t seg_lo = q0 * ch / kDecodeS;
+            int64_t nseg = ((q1 + 1) * ch - 1) / kDecodeS - seg_lo + 1;
+            nseg = nseg > kResSegs ? kResSegs : nseg;
+            __syncthreads();  // the previous stretch's symbols are no longer read
+            if (tid < 32) slut[tid] = f.lut[tid];
+            for (int i = tid; i < (int)nseg; i += kResThreads) {
+                uint16_t* o = ssym + i * kDecodeS;
+                if (!unpack_crop_segment(job, f, seg_lo + i, o))
+                    for (int z = 0; z < kDecodeS; ++z) o[z] = 0;
+            }
+            __syncthreads();
+            int64_t ua = fs + q0 * cs, ub = fs + (q1 + 1) * cs;
+            ua = ua < xa ? xa : ua;
+            ub = ub > xb ? xb : ub;
+            const int64_t n = (ub - ua) * ch;
+            for (int64_t l = tid; l < n; l += kResThreads) {
+                const int64_t s = ua + l / ch;
+                const int k = (int)(l % ch);
+                const int64_t local = s - fs;
+                const int64_t si = local / cs * ch + k, rel = si - seg_lo * kDecodeS;
+                int16_t v = 0;
+                if (rel >= 0 && rel < nseg * kDecodeS && si < f.nsym)
+                    v = table_sample(f, slut, ssym[rel], (int)(local % cs), StagedTables{}, g);
+                const int64_t di = (s - ia) * ch + k;
+                if (di >= 0 && di < src_cap) ssrc[di] = v;
+            }
+        }
+    }
+}
+
+// Outputs [t0, t1) of one crop's row, a tile of at most tile_len, by a whole
+// workgroup (crop_resample_kernel, crop_resample_bound_kernel, mix_resample_kernel):
+// write(ua, ub, value) gets the outputs of a pass, blank(ua, ub) what lies past
+// the crop's clipped length or belongs to a job that fails a check.  ssrc holds
+// src_cap int16, ssym kResSegs segments, slut 32 words.  write and blank are the
+// caller's sink: the crop kernels store, the mix kernels accumulate.
+template <typename Write, typename Blank>
+__device__ __forceinline__ void resample_run(const CropJob& job, int64_t t0, int64_t t1, int tile_len, int channels,
+                                             int src_cap, int16_t* ssrc, uint16_t* ssym, int* slut, Write write,
+                                             Blank blank) {
+    const int tid = threadIdx.x;
+    const int L = job.rate_up, M = job.rate_down, H = job.half_taps, C = job.src_ch;
+    const int taps = 2 * H, before = H > 0 ? H - 1 : 0;
+    // what the 32-bit position arithmetic of a pass and the LDS indices rely on
+    bool ok = job.f0 >= 0 && job.f0 < job.f1 && job.f1 <= job.nframes && L > 0 && L <= (1 << 17) && M > 0 &&
+              M <= (1 << 21) && H >= 0 && taps <= kResampleMaxTaps && (H == 0 || job.table != nullptr) && C > 0 &&
+              C <= 255 && job.out_ch == channels && (C == channels || C == 1 || channels == 1) && job.begin >= 0 &&
+              job.begin <= ((int64_t)1 << 40) && job.src_begin >= 0 && job.src_begin <= job.src_end;
+    const int64_t cap = ok ? src_cap / C : 0;  // source samples per channel of a pass
+    ok = ok && cap - taps - 2 >= 0;
+    // outputs per pass: n outputs read at most (n - 1) * M / L + taps + 2 source samples
+    int64_t sub = ok ? (cap - taps - 2) * L / M + 1 : 1;
+    sub = sub > tile_len ? tile_len : sub;
+    const int64_t tc = !ok ? t0 : (job.count < t1 ? (job.count > t0 ? job.count : t0) : t1);
+    blank(tc, t1);
+    for (int64_t na = t0; na < tc; na += sub) {
+        const int64_t nb = na + sub < tc ? na + sub : tc;
+        // output n sits at source position (begin * L + n * M) / L; within a pass the offset fits 32 bits
+        const int64_t p = job.begin * L + na * M;
+        const int64_t bi = p / L;
+        const uint32_t br = (uint32_t)(p - bi * L);
+        const uint32_t ul = br + (uint32_t)(nb - 1 - na) * (uint32_t)M;
+        const int64_t ia = bi - before, ib = bi + ul / (uint32_t)L + H;  // the span, both ends included
+        const int64_t span = ib - ia + 1;
+        if (span > cap) {  // never, by the choice of sub
+            blank(na, nb);
+            continue;
+        }
+        __syncthreads();  // the previous pass's span is no longer read
+        for (int i = tid; i < (int)span * C; i += kResThreads) ssrc[i] = 0;
+        __syncthreads();
+        const int64_t sa = ia > job.src_begin ? ia : job.src_begin, sb = ib + 1 < job.src_end ? ib + 1 : job.src_end;
+        if (sa < sb) resample_fill(job, sa, sb, ia, C, ssrc, (int)span * C, ssym, slut, tid);
+        __syncthreads();
+        // channel k of the output at offset u = br + (n - na) * M of the pass
+        auto one = [&](uint32_t qi, const int32_t* __restrict__ row, int k) {
+            const int16_t* x = ssrc + (int)qi * C + k;  // (qi + taps - 1) * C + k < span * C
+            if (H == 0) return (int)x[0];
+            int64_t acc = 0;
+            for (int j = 0; j < taps; ++j) acc += (int64_t)row[j] * (int64_t)x[j * C];
+            const int64_t y = (acc + ((int64_t)1 << (kResampleShift - 1))) >> kResampleShift;
+            return (int)(y < -32768 ? -32768 : (y > 32767 ? 32767 : y));
+        };
+        write(na, nb, [&](int64_t n, int c) {
+            const uint32_t u = br + (uint32_t)(n - na) * (uint32_t)M;
+            const uint32_t qi = u / (uint32_t)L, phase = u - qi * (uint32_t)L;
+            const int32_t* row = job.table + (int64_t)phase * taps;
+            if (C == channels) return (int16_t)one(qi, row, c);
+            if (C == 1) return (int16_t)one(qi, row, 0);
+            int sum = 0;  // channels == 1: the mean, rounded half up
+            for (int k = 0; k < C; ++k) sum += one(qi, row, k);
+            const int num = 2 * sum + C, den = 2 * C;
+            int q = num / den;
+            q -= (num % den < 0) ? 1 : 0;
+            return (int16_t)q;
+        });
+    }
+}
+
 
 // f(T{}, std::bool_constant<PLANAR>{}) for the output's element type and layout
 template <typename F>

@@ -113,6 +113,12 @@ hipError_t gsc_launch_crop_resample_bound(const gsc::BoundStream* streams, int n
                                           int src_samples, void* out, int64_t* written, hipStream_t st);
 hipError_t gsc_prepare_crop_resample_bound(int src_samples);
 
+// ---- gsc_decode_mix.hip
+hipError_t gsc_launch_crop_mix(const gsc::BoundStream* streams, int nstreams, const int64_t* sources, int nrows,
+                               int nsrc, int64_t length, int channels, int is_float, int planar, int resample,
+                               int src_samples, void* out, int64_t* written, hipStream_t st);
+hipError_t gsc_prepare_crop_mix(int channels, int src_samples);
+
 // ---- gsc_decode_envelope.hip
 hipError_t gsc_launch_envelope(const gsc::BoundStream* streams, int nstreams, const int64_t* layout, int64_t ntiles,
                                int hop, int64_t* energy, int32_t* peak, int64_t nblocks, hipStream_t st);

@@ -12,7 +12,8 @@ straight into a torch tensor on the device, and ``decode_samples`` one range to
 numpy.  ``Decoder.open_many(gscs, tables)`` opens a whole corpus as one
 ``StreamSet`` at a fixed number of runtime calls.  ``Decoder.bind(streams)``
 describes streams once on the device (``CropBinding``), whose ``decode_crops``
-takes the crops from a device tensor, and whose ``envelope`` gives the block
+takes the crops from a device tensor, whose ``mix`` sums several crops per row
+with integer gains in the same launch, and whose ``envelope`` gives the block
 energy and peak of every bound stream (``Envelope``), from which
 ``Envelope.sample_crops`` draws crops where there is sound, and whose
 ``fidelity`` gives the block error energy of every bound stream against its
@@ -325,6 +326,7 @@ class CropBinding:
         self._owners = list(owners.values())
         self.channels = streams[0].channels if channels is None else int(channels)
         self.rate = None if rate is None else int(rate)
+        self._converts = rate is not None or channels is not None  # the resampling kernels, not the fused ones
         self.device = torch.device("cuda", streams[0].device)
         hs = (ctypes.c_void_p * len(streams))(*[s._handle() for s in streams])
         with torch.cuda.device(self.device):
@@ -358,38 +360,100 @@ class CropBinding:
         if crops.dtype != torch.int64 or crops.dim() != 2 or crops.shape[1] != 3 or not crops.is_contiguous():
             raise _lib.GscError(f"bound decode_crops: crops must be a contiguous torch.int64 tensor [B, 3], got "
                                 f"{crops.dtype} {tuple(crops.shape)}; Decoder.decode_crops takes crops as a host list")
+        length, out, written, pcm, lay = self._row_outputs("bound decode_crops", crops.shape[0], length, dtype, layout,
+                                                           out, written)
+        B = crops.shape[0]
+        with torch.cuda.device(device):
+            hip_stream = ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+            _lib.check(_lib.load().gsc_crop_binding_decode(self._h, crops.data_ptr(), B, pcm, lay, length,
+                                                           out.data_ptr(), written.data_ptr(), hip_stream))
+        return out, written
+
+    def _row_outputs(self, who, B, length, dtype, layout, out, written):
+        """What a call that writes B rows checks and makes: (length, out, written, pcm, lay)."""
+        import torch
+
+        device = self.device
         dtype = torch.int16 if dtype is None else dtype
         if dtype not in (torch.int16, torch.float32):
-            raise _lib.GscError(f"bound decode_crops: dtype {dtype} is neither torch.int16 nor torch.float32")
+            raise _lib.GscError(f"{who}: dtype {dtype} is neither torch.int16 nor torch.float32")
         if layout not in ("TC", "CT"):
-            raise _lib.GscError(f"bound decode_crops: layout {layout!r} is neither 'TC' nor 'CT'")
+            raise _lib.GscError(f"{who}: layout {layout!r} is neither 'TC' nor 'CT'")
         length = int(length)
         if length < 0:
-            raise _lib.GscError(f"bound decode_crops: length {length}")
-        B, ch = crops.shape[0], self.channels
+            raise _lib.GscError(f"{who}: length {length}")
+        ch = self.channels
         shape = (B, length, ch) if layout == "TC" else (B, ch, length)
         if out is None:
             out = torch.empty(shape, dtype=dtype, device=device)
         else:
             if out.device != device:
-                raise _lib.GscError(f"bound decode_crops: out is on {out.device}, the streams live on {device}")
+                raise _lib.GscError(f"{who}: out is on {out.device}, the streams live on {device}")
             if out.dtype != dtype or tuple(out.shape) != shape or not out.is_contiguous():
-                raise _lib.GscError(f"bound decode_crops: out must be a contiguous {dtype} tensor of shape {shape}, "
+                raise _lib.GscError(f"{who}: out must be a contiguous {dtype} tensor of shape {shape}, "
                                     f"got {out.dtype} {tuple(out.shape)}")
         if written is None:
             # without a row to write the library launches nothing and reports nothing
             written = (torch.empty if length else torch.zeros)((B,), dtype=torch.int64, device=device)
         elif (written.device != device or written.dtype != torch.int64 or tuple(written.shape) != (B,) or
               not written.is_contiguous()):
-            raise _lib.GscError(f"bound decode_crops: written must be a contiguous torch.int64 tensor [{B}] on "
+            raise _lib.GscError(f"{who}: written must be a contiguous torch.int64 tensor [{B}] on "
                                 f"{device}")
         pcm = _lib.PCM_FLOAT32 if dtype == torch.float32 else _lib.PCM_INT16
         lay = _lib.LAYOUT_CT if layout == "CT" else _lib.LAYOUT_TC
+        return length, out, written, pcm, lay
+
+    def mix(self, sources, length: int, dtype=None, layout: str = "TC", out=None, written=None):
+        """Gain-weighted sums of crops (include/soundchunks.h "mixing crops").
+        ``sources``: a contiguous ``torch.int64`` tensor [R, K, 4] of (stream
+        index, begin, count, gain) on the streams' device, 1 <= K <= 256;
+        (stream, begin, count) is a crop of ``decode_crops``, ``gain`` is Q15
+        (32768 is unity, ``round(g * 32768)`` for a linear gain g) within
+        +-2**20.  Row r is ``clamp((sum_k gain_k * x_k + 16384) >> 15)`` of its K
+        crops ``x_k`` in exact integer arithmetic; a slot with ``count == 0``
+        adds nothing.  Returns ``(x, n)`` shaped as ``decode_crops`` returns
+        them: ``n[r]`` is the largest clipped count of the row's sources.  A row
+        with one bad source (a bad crop, or a gain out of range) is all zero and
+        has ``n[r] == -1``; the other rows do not notice.  The work is one
+        kernel on torch's current stream; nothing is synchronised, allocated or
+        copied by the library, and no source is read on the host.
+
+        A list or numpy array is accepted for ``sources`` as a convenience: the
+        wrapper uploads it, which is a copy outside that contract."""
+        import torch
+
+        self._check_open()
+        device = self.device
+        if not isinstance(sources, torch.Tensor):
+            try:
+                host = np.asarray(sources)
+            except Exception as e:
+                raise _lib.GscError(f"mix: sources: {e}") from None
+            if host.dtype.kind not in "iu":
+                raise _lib.GscError(f"mix: sources must be integers, got {host.dtype}")
+            sources = torch.from_numpy(np.ascontiguousarray(host, dtype=np.int64)).to(device)
+        if sources.device != device:
+            raise _lib.GscError(f"mix: sources must be a torch.int64 tensor [R, K, 4] on {device}, got "
+                                f"{sources.device}")
+        if sources.dtype != torch.int64 or sources.dim() != 3 or sources.shape[2] != 4 or not sources.is_contiguous():
+            raise _lib.GscError(f"mix: sources must be a contiguous torch.int64 tensor [R, K, 4], got {sources.dtype} "
+                                f"{tuple(sources.shape)}")
+        R, K = sources.shape[0], sources.shape[1]
+        if K < 1 or K > 256:
+            raise _lib.GscError(f"mix: {K} sources per row, 1 to 256 are possible")
+        length, out, written, pcm, lay = self._row_outputs("mix", R, length, dtype, layout, out, written)
         with torch.cuda.device(device):
             hip_stream = ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-            _lib.check(_lib.load().gsc_crop_binding_decode(self._h, crops.data_ptr(), B, pcm, lay, length,
-                                                           out.data_ptr(), written.data_ptr(), hip_stream))
+            _lib.check(_lib.load().gsc_crop_binding_mix(self._h, sources.data_ptr(), R, K, pcm, lay, length,
+                                                        out.data_ptr(), written.data_ptr(), hip_stream))
         return out, written
+
+    def mix_tile(self) -> int:
+        """Output samples of one workgroup of ``mix`` for this binding: what 4096 accumulators
+        (kMixAccElems, csrc/gsc_mix.h) hold of its channels, at most ``Decoder.resample_tile()``
+        when the binding converts."""
+        fit = max(1, 4096 // self.channels)
+        return min(fit, Decoder.resample_tile()) if self._converts else fit
 
     def envelope(self, hop: int = 1024, energy=None, peak=None) -> "Envelope":
         """Block energy and peak of every bound stream (include/soundchunks.h
@@ -511,7 +575,7 @@ class CropBinding:
 
     @staticmethod
     def last_call() -> dict:
-        """The runtime calls of this thread's last ``decode_crops`` of a binding, and its host time."""
+        """The runtime calls of this thread's last ``decode_crops`` or ``mix`` of a binding, and its host time."""
         s = _lib.GscCropCallStats()
         _lib.load().gsc_crop_binding_last_call(ctypes.byref(s))
         return {k: getattr(s, k) for k, _ in s._fields_}
