@@ -166,6 +166,11 @@ int gsc_frame_dsp(const uint8_t *wav, size_t wav_len, const gsc_options *o, int 
 
 /* Stage entry points on host buffers (row-major), used by parity tests. */
 int gsc_yakmo_seed_means(int n, int d, const float *x, int k, float *centroids);
+/* The same for nf frames in one launch, an n and a k per frame: x, centroids
+ * and labels (the seeding assignment; may be NULL) hold the frames' arrays one
+ * after another (ns[i] x d, ks[i] x d, ns[i]). */
+int gsc_yakmo_seed_means_frames(int nf, int d, const int *ns, const float *x, const int *ks, float *centroids,
+                                int *labels);
 int gsc_scan_reduce(int n, int d, const float *x, int k, float *centroids, int *clusters, int precision, int *iters);
 /* -py reducer stage (cluster.py Birch labels, extern.pas:350-437): n x d
  * Single features of one frame -> labels[n] in [0, k). */

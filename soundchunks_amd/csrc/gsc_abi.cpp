@@ -145,7 +145,8 @@ void yakmo_train_on_data(yakmo_t* ay, int* pointToCluster) {
     fr.N = N;
     fr.K = K;
     fr.k_off = N;
-    Dev<float> dX(ay->data.size()), dC(size_t(K) * D), dF(4 * size_t(N));
+    // (dF: 64 floats of slack, the pick's replay loads whole 64-point rows of d0)
+    Dev<float> dX(ay->data.size()), dC(size_t(K) * D), dF(4 * size_t(N) + 64);
     Dev<int> dI(size_t(N) + K);
     Dev<uint32_t> dB(gsc_yakmo_big_words(N, 1));
     Dev<float> dS(gsc_yakmo_big_floats(N, 1));

@@ -419,34 +419,50 @@ int gsc_yakmo_chain_test(int ppl, const float* pts, int nbk, float run, int* acc
     return 0;
 }
 
-// yakmo's seeding alone (no KNNScanReduce pass): the seeds of one frame
-int gsc_yakmo_seed_means(int n, int d0, const float* x, int k, float* centroids) {
+// yakmo's seeding alone (no KNNScanReduce pass) of several frames in ONE launch,
+// with an N and a K per frame: x / centroids / labels are the frames' arrays
+// one after another (ns[i] x d0, ks[i] x d0, ns[i]); labels (may be null) is the
+// seeding assignment.  A frame over gsc_yakmo_max_lds_points() puts every frame
+// of the launch on the kernel's HBM instantiation.
+int gsc_yakmo_seed_means_frames(int nf, int d0, const int* ns, const float* x, const int* ks, float* centroids,
+                                int* labels) {
     if (require_device() != 0) return -1;
-    if (k >= n || k <= 0 || k > kMaxK) return set_last_error("yakmo needs 0 < k < n, k <= 4096");
+    if (nf <= 0 || !ns || !ks || !x || !centroids) return set_last_error("gsc_yakmo_seed_means_frames: invalid argument");
+    for (int i = 0; i < nf; ++i)
+        if (ks[i] >= ns[i] || ks[i] <= 0 || ks[i] > kMaxK) return set_last_error("yakmo needs 0 < k < n, k <= 4096");
     if (d0 <= 0 || d0 > 32) return set_last_error("yakmo: 1 <= d <= 32 features");
     const int d = feature_stride((d0 + 1) / 2);  // the kernel width; trailing zero features change nothing
-    std::vector<float> X = pad_rows(x, n, d0, d), C;
-    const ReduceLayout L = reduce_layout(1, &n, &k, nullptr, d, 0);
+    const ReduceLayout L = reduce_layout(nf, ns, ks, nullptr, d, 0);
+    const int nsum = int(L.points), ksum = int(L.nC / size_t(d));
+    const std::vector<float> X = pad_rows(x, nsum, d0, d);
+    std::vector<float> C(L.nC);
     DevBuf<float> dX, dC, dF, dYSum;
     DevBuf<int> dI;
     DevBuf<uint32_t> dBits;
     DevBuf<ReduceFrame> dFr;
     HIP_TRY(dX.alloc(X.size()));
     HIP_TRY(dC.alloc(L.nC));
-    HIP_TRY(dF.alloc(L.nF));
+    // (the pick's replay loads whole 64-point rows of d0: a last frame of fewer
+    // than 22 points would read past its 4 N floats)
+    HIP_TRY(dF.alloc(L.nF + 64));
     HIP_TRY(dI.alloc(L.nI));
-    HIP_TRY(dBits.alloc(gsc_yakmo_big_words(n, 1)));
-    HIP_TRY(dYSum.alloc(gsc_yakmo_big_floats(n, 1)));
-    HIP_TRY(dFr.alloc(1));
+    HIP_TRY(dBits.alloc(gsc_yakmo_big_words(L.points, nf)));
+    HIP_TRY(dYSum.alloc(gsc_yakmo_big_floats(L.points, nf)));
+    HIP_TRY(dFr.alloc(size_t(nf)));
     HIP_TRY(hipMemcpy(dX.p, X.data(), sizeof(float) * X.size(), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(dFr.p, L.frames.data(), sizeof(ReduceFrame), hipMemcpyHostToDevice));
-    HIP_TRY(gsc_launch_yakmo(d, dFr.p, 1, dX.p, dC.p, dF.p, dI.p, dYSum.p, dBits.p, n, nullptr));
+    HIP_TRY(hipMemcpy(dFr.p, L.frames.data(), sizeof(ReduceFrame) * size_t(nf), hipMemcpyHostToDevice));
+    HIP_TRY(gsc_launch_yakmo(d, dFr.p, nf, dX.p, dC.p, dF.p, dI.p, dYSum.p, dBits.p, L.max_n, nullptr));
     HIP_TRY(hipDeviceSynchronize());
-    C.resize(size_t(k) * d);
-    HIP_TRY(hipMemcpy(C.data(), dC.p, sizeof(float) * size_t(k) * d, hipMemcpyDeviceToHost));
-    compact_rows(&C, k, d, d0);
-    std::memcpy(centroids, C.data(), sizeof(float) * size_t(k) * d0);
+    HIP_TRY(hipMemcpy(C.data(), dC.p, sizeof(float) * C.size(), hipMemcpyDeviceToHost));
+    compact_rows(&C, ksum, d, d0);
+    std::memcpy(centroids, C.data(), sizeof(float) * size_t(ksum) * d0);
+    if (labels) HIP_TRY(hipMemcpy(labels, dI.p, sizeof(int) * size_t(nsum), hipMemcpyDeviceToHost));
     return 0;
+}
+
+// the seeds of one frame
+int gsc_yakmo_seed_means(int n, int d0, const float* x, int k, float* centroids) {
+    return gsc_yakmo_seed_means_frames(1, d0, &n, x, &k, centroids, nullptr);
 }
 
 int gsc_scan_reduce(int n, int d0, const float* x, int k, float* centroids, int* clusters, int precision, int* iters) {

@@ -300,6 +300,22 @@ def yakmo_seed_means(x: np.ndarray, k: int) -> np.ndarray:
     return c
 
 
+def yakmo_seed_means_many(frames: Sequence[np.ndarray], ks: Sequence[int]):
+    """yakmo seeding of several frames (N_i x D float32, one D) in ONE launch, a K
+    per frame; returns (centroids per frame, seeding labels per frame)."""
+    xs = [np.ascontiguousarray(f, dtype=np.float32) for f in frames]
+    d = xs[0].shape[1]
+    assert len(xs) == len(ks) and all(x.ndim == 2 and x.shape[1] == d for x in xs)
+    ns = np.array([x.shape[0] for x in xs], dtype=np.int32)
+    kv = np.array(ks, dtype=np.int32)
+    x = np.ascontiguousarray(np.concatenate(xs, axis=0))
+    c = np.zeros((int(kv.sum()), d), dtype=np.float32)
+    lab = np.zeros(int(ns.sum()), dtype=np.int32)
+    _lib.check(_lib.load().gsc_yakmo_seed_means_frames(len(xs), d, _ip(ns), _fp(x), _ip(kv), _fp(c), _ip(lab)))
+    ko, no = np.concatenate([[0], np.cumsum(kv)]), np.concatenate([[0], np.cumsum(ns)])
+    return ([c[ko[i]:ko[i + 1]] for i in range(len(xs))], [lab[no[i]:no[i + 1]] for i in range(len(xs))])
+
+
 def scan_reduce(x: np.ndarray, c0: np.ndarray, precision: int = 3):
     """KNNScanReduce on the GPU; returns (centroids, clusters, passes)."""
     x = np.ascontiguousarray(x, dtype=np.float32)
