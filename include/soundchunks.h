@@ -176,6 +176,12 @@ int gsc_scan_reduce(int n, int d, const float *x, int k, float *centroids, int *
  * Single features of one frame -> labels[n] in [0, k). */
 int gsc_birch_labels(int n, int d, const float *x, int k, int *labels);
 int gsc_knnfit_assign(int r, int cs, const float *cand_fwd, int n, const float *q, float eps, int *best);
+/* The same for nf frames in one launch, an r, an n and an eps per frame:
+ * cand_fwd, q and best hold the frames' arrays one after another (rs[i] x cs,
+ * ns[i] x cs, ns[i]).  overflow[i] (may be NULL) is the number of frame i's
+ * queries whose tie set exceeded the 64-NN bucket (answered by the ANN replay). */
+int gsc_knnfit_assign_frames(int nf, int cs, const int *rs, const float *cand_fwd, const int *ns, const float *q,
+                             const float *eps, int *best, int *overflow);
 /* yakmo's prefix-chain fast path (gsc_yakmo.hip chain_fast, ppl = 8 or 16
  * points per lane) on 64*nbk points from *run: the accepted block count, the
  * run after them, and per accepted block the checkpoint / min / max of the

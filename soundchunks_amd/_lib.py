@@ -199,6 +199,7 @@ SIGNATURES = {
     "gsc_scan_reduce": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, _FP, ctypes.c_int, _FP, _IP, ctypes.c_int, _IP]),
     "gsc_birch_labels": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, _FP, ctypes.c_int, _IP]),
     "gsc_knnfit_assign": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, _FP, ctypes.c_int, _FP, ctypes.c_float, _IP]),
+    "gsc_knnfit_assign_frames": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, _IP, _FP, _IP, _FP, _FP, _IP, _IP]),
     "gsc_index_create": (ctypes.c_void_p, [_U8P, ctypes.c_size_t]),
     "gsc_index_frame_count": (ctypes.c_int, [ctypes.c_void_p]),
     "gsc_index_info": (ctypes.c_int, [ctypes.c_void_p, _IP, _IP, _LLP]),

@@ -460,7 +460,8 @@ __device__ __forceinline__ void knn_chunk_dists(const float (&q)[CS], const floa
 // eps_b = (|q|^2 + vmax) 2^-17 of the exact sequential distance (error budget:
 // fma dot <= CS u (|q|^2 + |v|^2)/2 x 2, norms <= CS u each, two adds, the
 // exact sum <= (CS + 1) u x 2 (|q|^2 + |v|^2): < 90 u for CS <= 16, against
-// 128 u).  The exact distances are computed only where the bounds cannot decide:
+// 128 u; 2^-140 is added for denormal squares, whose rounding is absolute, up to
+// 2^-150 per operation).  The exact distances are computed only where the bounds cannot decide:
 // pass 1 evaluates a candidate exactly only while its bound is within 2 eps_b of
 // the running minimum bound (the exact minimum always is, as the threshold only
 // falls); pass 2 only where some variant's bound may reach the acceptance
@@ -504,7 +505,9 @@ __global__ __launch_bounds__(256) void knnfit_kernel(FitFrame* __restrict__ fram
 #pragma unroll
     for (int j = 0; j < CS; ++j) qq = __fmaf_rn(q[j], q[j], qq);
     __syncthreads();
-    const float eb = (qq + __uint_as_float(s_vmax)) * 7.62939453e-06f;  // 2^-17
+    // 2^-17 relative, plus 2^-140 absolute: where the squares are denormal every operation's
+    // rounding is up to 2^-150 whatever its size (bound and exact sum < 70 of them, ehi < 20)
+    const float eb = (qq + __uint_as_float(s_vmax)) * 7.62939453e-06f + __uint_as_float(512u);
     float e0 = __builtin_inff(), mt = __builtin_inff();
     float s0 = 0.0f, ehi = 0.0f;
     int best = -1, cnt = 0;

@@ -1,7 +1,7 @@
 // Host side of TFrame.KNNFit outside the encode pipeline: the overflow replay
 // through ANN's priority search (run_knnfit_overflow, also called by the
-// pipeline's post_group), the synchronous batch driver and its drop-in entry
-// point gsc_knnfit_assign.
+// pipeline's post_group), the synchronous batch driver and its entry points
+// gsc_knnfit_assign_frames (several frames, one launch) and gsc_knnfit_assign.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -146,10 +146,11 @@ int run_knnfit_overflow(int CS, const std::vector<FitFrame>& fr, const std::vect
 
 namespace {
 
-// KNNFit of whole frames from host arrays, synchronously; knn_ms: the kernel's and the replay's time
+// KNNFit of whole frames from host arrays, synchronously; knn_ms: the kernel's and the replay's time;
+// overflow (may be null): per frame, the queries the brute-force kernel flagged for the replay
 int run_knnfit_batch(int CS, const std::vector<int>& Rs, const std::vector<int>& Ns, const std::vector<float>& eps,
                      const std::vector<float>& cand, const std::vector<float>& q, std::vector<int>* best,
-                     double* knn_ms) {
+                     double* knn_ms, std::vector<int>* overflow) {
     const int nf = int(Ns.size());
     if (nf == 0) return 0;
     std::vector<FitFrame> fr(static_cast<size_t>(nf));
@@ -192,8 +193,11 @@ int run_knnfit_batch(int CS, const std::vector<int>& Rs, const std::vector<int>&
     HIP_TRY(hipMemcpy(best->data(), dOut.p, sizeof(int) * best->size(), hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(fr.data(), dFr.p, sizeof(FitFrame) * size_t(nf), hipMemcpyDeviceToHost));
     std::vector<int> ov_frames;
-    for (int i = 0; i < nf; ++i)
+    if (overflow) overflow->assign(size_t(nf), 0);
+    for (int i = 0; i < nf; ++i) {
         if (fr[i].overflow > 0) ov_frames.push_back(i);
+        if (overflow) (*overflow)[size_t(i)] = fr[i].overflow;
+    }
     if (!ov_frames.empty()) {
         const double t0 = now_ms();
         DevArena arena;  // synchronous call: freed on return, after the stream sync
@@ -206,12 +210,39 @@ int run_knnfit_batch(int CS, const std::vector<int>& Rs, const std::vector<int>&
 }  // namespace
 }  // namespace gsc
 
-extern "C" int gsc_knnfit_assign(int r, int cs, const float* cand_fwd, int n, const float* q, float eps, int* best) {
+// KNNFit of nf frames in ONE launch, an r, an n and an eps per frame: cand_fwd,
+// q and best hold the frames' arrays one after another (rs[i] x cs, ns[i] x cs,
+// ns[i]); overflow[i] (may be null) counts frame i's queries whose tie set
+// exceeded the 64-NN bucket, which the ANN replay answered.
+extern "C" int gsc_knnfit_assign_frames(int nf, int cs, const int* rs, const float* cand_fwd, const int* ns,
+                                        const float* q, const float* eps, int* best, int* overflow) {
+    using gsc::set_last_error;
     if (gsc::require_device() != 0) return -1;
-    std::vector<int> Rs{r}, Ns{n}, out;
-    std::vector<float> E{eps}, C(cand_fwd, cand_fwd + size_t(r) * cs), Q(q, q + size_t(n) * cs);
+    if (nf <= 0) return set_last_error("gsc_knnfit_assign_frames: nf must be positive");
+    if (cs < 1 || cs > 16) return set_last_error("gsc_knnfit_assign_frames: cs outside 1..16");
+    if (!rs) return set_last_error("gsc_knnfit_assign_frames: rs is null");
+    if (!cand_fwd) return set_last_error("gsc_knnfit_assign_frames: cand_fwd is null");
+    if (!ns) return set_last_error("gsc_knnfit_assign_frames: ns is null");
+    if (!q) return set_last_error("gsc_knnfit_assign_frames: q is null");
+    if (!eps) return set_last_error("gsc_knnfit_assign_frames: eps is null");
+    if (!best) return set_last_error("gsc_knnfit_assign_frames: best is null");
+    size_t rsum = 0, nsum = 0;
+    for (int i = 0; i < nf; ++i) {
+        if (rs[i] < 1) return set_last_error("gsc_knnfit_assign_frames: every r must be at least 1");
+        if (ns[i] < 1) return set_last_error("gsc_knnfit_assign_frames: every n must be at least 1");
+        rsum += size_t(rs[i]);
+        nsum += size_t(ns[i]);
+    }
+    std::vector<int> Rs(rs, rs + nf), Ns(ns, ns + nf), out, ov;
+    std::vector<float> E(eps, eps + nf), C(cand_fwd, cand_fwd + rsum * size_t(cs)), Q(q, q + nsum * size_t(cs));
     double ms = 0;
-    if (gsc::run_knnfit_batch(cs, Rs, Ns, E, C, Q, &out, &ms) != 0) return -1;
-    std::memcpy(best, out.data(), sizeof(int) * size_t(n));
+    if (gsc::run_knnfit_batch(cs, Rs, Ns, E, C, Q, &out, &ms, &ov) != 0) return -1;
+    std::memcpy(best, out.data(), sizeof(int) * nsum);
+    if (overflow) std::memcpy(overflow, ov.data(), sizeof(int) * size_t(nf));
     return 0;
+}
+
+// one frame
+extern "C" int gsc_knnfit_assign(int r, int cs, const float* cand_fwd, int n, const float* q, float eps, int* best) {
+    return gsc_knnfit_assign_frames(1, cs, &r, cand_fwd, &n, q, &eps, best, nullptr);
 }

@@ -346,6 +346,28 @@ def knnfit_assign(cand_fwd: np.ndarray, q: np.ndarray, eps: float) -> np.ndarray
     return out
 
 
+def knnfit_assign_many(cands: Sequence[np.ndarray], qs: Sequence[np.ndarray], epss: Sequence[float]):
+    """KNNFit of several frames (forward candidates R_i x CS, queries N_i x CS, one
+    CS) in ONE launch, an eps per frame; returns (best per frame, per frame the
+    number of queries whose tie set overflowed the 64-NN bucket)."""
+    cs_ = [np.ascontiguousarray(c, dtype=np.float32) for c in cands]
+    qs_ = [np.ascontiguousarray(q, dtype=np.float32) for q in qs]
+    assert len(cs_) == len(qs_) == len(epss)
+    cs = cs_[0].shape[1] if cs_ else 0
+    assert all(a.ndim == 2 and a.shape[1] == cs for a in cs_ + qs_)
+    rs = np.array([c.shape[0] for c in cs_], dtype=np.int32)
+    ns = np.array([q.shape[0] for q in qs_], dtype=np.int32)
+    cand = np.ascontiguousarray(np.concatenate(cs_, axis=0)) if cs_ else np.zeros((0, 0), np.float32)
+    q = np.ascontiguousarray(np.concatenate(qs_, axis=0)) if qs_ else np.zeros((0, 0), np.float32)
+    ev = np.array(epss, dtype=np.float32)
+    best = np.zeros(int(ns.sum()), dtype=np.int32)
+    ov = np.zeros(len(cs_), dtype=np.int32)
+    _lib.check(_lib.load().gsc_knnfit_assign_frames(len(cs_), cs, _ip(rs), _fp(cand), _ip(ns), _fp(q), _fp(ev),
+                                                    _ip(best), _ip(ov)))
+    no = np.concatenate([[0], np.cumsum(ns)])
+    return [best[no[i]:no[i + 1]] for i in range(len(cs_))], ov.tolist()
+
+
 def frame_dsp(wav: bytes, frame: int = 0, argv: Sequence[str] = ()) -> tuple[int, np.ndarray]:
     """Device DSP of one frame: (attenuation divider, N x 2CS features)."""
     o = parse_options(argv)
